@@ -189,14 +189,15 @@ class Stepper:
 
     def __init__(self, step, ring, device, mode):
         self.step, self.ring, self.R, self.device, self.mode = step, ring, int(ring.shape[0]), device, mode
-        self.graphs = {}
+        self.graphs, self.graph_out, self.last_out = {}, {}, None
 
     def _capture(self, n):
         g = torch.cuda.CUDAGraph()
         # thread_local: the RCCL watchdog thread of a multi-rank run may touch the runtime during capture
         with torch.cuda.graph(g, capture_error_mode="thread_local"):
             for i in range(n):
-                self.step(self.ring[i])
+                out = self.step(self.ring[i])
+        self.graph_out[n] = out   # the buffers a replay of this graph leaves its last step's results in
         return g
 
     def prepare(self, K):
@@ -233,9 +234,43 @@ class Stepper:
                 self.graphs[self.R].replay()
             if rem:
                 self.graphs[rem].replay()
+            self.last_out = self.graph_out[rem or self.R]
         else:
             for i in range(K):
-                self.step(self.ring[i % self.R])
+                out = self.step(self.ring[i % self.R])
+            self.last_out = out
+
+
+DUMP_BYTES = 64 * 10 ** 6
+
+
+def dump_outputs(path, out, packed_flags, rank=0, world=1):
+    """--dump-outputs: what the timed path's last step returned to its caller -- observations, rewards, dones and the tensors of
+    its info dict (distance / reset_mask / ended / truncated) -- as <path>/<name>.npy in float32 (or float64 where the path
+    computes in it); dones and masks become 0.0 / 1.0.  More than 64 MB in all: a fixed, seeded sample of env indices (the same
+    rows of every array), saved beside them as env_index.npy.  Ranks > 0 of a multi-GPU run prefix their files with rank<r>_."""
+    obs, rew, done, info = out
+    arrays = {"obs": obs, "rew": rew}
+    if packed_flags:   # raw done bytes with the episode flags in bits 1..3: split them like a caller would
+        from gym_uav_collision_avoidance_amd import BatchedMultiUAVWorld2D
+        arrays["done"], arrays["reset_mask"], arrays["ended"], arrays["truncated"] = BatchedMultiUAVWorld2D.unpack_done(done)
+    else:
+        arrays["done"] = done
+        arrays.update((k, v) for k, v in info.items() if isinstance(v, torch.Tensor))
+    arrays = {k: (v if v.dtype in (torch.float32, torch.float64) else v.to(torch.float32)) for k, v in arrays.items()}
+    E = int(obs.shape[0])
+    budget = DUMP_BYTES // world - 4096   # (room for the .npy headers)
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    if total > budget:
+        keep = max(1, budget * E // (total + 8 * E))
+        idx = np.sort(np.random.default_rng(0).choice(E, keep, replace=False))
+        sel = torch.from_numpy(idx).to(obs.device)
+        arrays = {k: v.index_select(0, sel) for k, v in arrays.items()}
+        arrays["env_index"] = torch.from_numpy(idx.astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    prefix = f"rank{rank}_" if rank else ""
+    for k, v in arrays.items():
+        np.save(os.path.join(path, f"{prefix}{k}.npy"), v.cpu().numpy())
 
 
 def event_passes(K):
@@ -373,7 +408,11 @@ def open_loop_point(E, N, device, gen, K=32, reps=40):
     env = BatchedMultiUAVWorld2D(E, num_agents=N, device=device, seed=0)
     env.reset()
     tape = polar_actions(gen, (K, E, N), float(np.sqrt(200.0)), device)
-    env.step_k(tape, tape_out=True)
+    # the loop below holds one call's output tapes while the next call allocates its own, so it cycles through TWO sets: both
+    # are allocated here, or the second set's hipMalloc (~350 MB at 65 536 x 4, milliseconds on a device other processes
+    # have just used) lands inside the bracket
+    out = env.step_k(tape, tape_out=True)
+    out = env.step_k(tape, tape_out=True)
     torch.cuda.synchronize(device)
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     ev0.record()
@@ -547,6 +586,9 @@ def main():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-large", action="store_true",
                     help="skip the extra measurements: the HBM-sized second roofline point (1 Mi envs) and roofline_steady")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last of them returned (obs, rewards, dones, info tensors) as "
+                         "DIR/<name>.npy (float32 / float64, at most 64 MB: a seeded sample of envs beyond that)")
     args = ap.parse_args()
     # dmabuf IPC.  The host driver of this pool supports no other kind: without this variable RCCL (and any sharing of device
     # memory between processes) fails with `hipIpcGetMemHandle: invalid argument` (the pool's environment notes; exported there
@@ -666,6 +708,9 @@ def main():
 
     walls = timed_regions(stepper, K, max(1, args.repeats), device, dist)
     devs = timed_regions(stepper, K, max(1, args.repeats), device, dist, events=True)   # device time, in regions of their own
+    if args.dump_outputs:   # after the timed steps, before anything else steps this env
+        torch.cuda.synchronize(device)
+        dump_outputs(args.dump_outputs, stepper.last_out, args.world == "multi" and args.fused and args.packed_flags, rank, world)
 
     # episode-metrics path (test_sac_multi.py:164-165): counters read + ONE gather to rank 0, timed on its own
     torch.cuda.synchronize(device)

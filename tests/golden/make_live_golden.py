@@ -1,0 +1,131 @@
+#!/usr/bin/env python3
+"""Records the REFERENCE env's side of tests/test_reference_live.py into tests/golden/live_*.npz.
+
+Run where the reference checkout is importable (see ref_loader.py):
+    python tests/golden/make_live_golden.py
+Each scenario of the three live cross-checks (seeds, agent counts, the actions fed, evaluate flags) is driven through the
+reference exactly as the tests drive the oracle, and what the tests compare is stored: the commands, the reference's
+observations after every reset, and per step its dones, positions, velocities, previous distances, flags, counters,
+rewards and observations.  Data only; the tests then need nothing outside the repository.
+"""
+import json
+import math
+import os
+import sys
+
+import numpy as np
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+sys.path.insert(0, HERE)
+import ref_loader  # noqa: E402
+
+# the scenarios of tests/test_reference_live.py (that module imports these lists)
+MUW_CASES = [(1, 101), (2, 102), (3, 103), (4, 104), (4, 105), (7, 106), (12, 107), (20, 108)]
+MUW_EPISODES, MUW_T = 3, 150
+UW_SEEDS = [201, 202]
+UW_EPISODES, UW_T = 3, 200
+F64_CASES = [(4, True), (6, True), (5, False), (3, False)]
+F64_T = 900
+
+
+def muw_kwargs(n, seed):
+    return dict(num_agents=n) if seed % 2 else dict(num_agents=n, x_size=30.0, y_size=36.0, d_sense=9, collider_radius=0.8)
+
+
+def snap(env):
+    ags = env.agent_list
+    return dict(loc=np.array([a.location for a in ags], np.float64), vel=np.array([a.velocity for a in ags], np.float64),
+                prev_d=np.array([a.prev_distance for a in ags], np.float64),
+                flags=np.array([(1 if a.done else 0) | (2 if a.collided else 0) for a in ags], np.uint8),
+                counters=np.array([env.steps, env.target_reach_count, env.collision_count], np.uint32))
+
+
+def record(rows, **fields):
+    for k, v in fields.items():
+        rows.setdefault(k, []).append(np.asarray(v))
+
+
+def save(name, data, meta):
+    meta = dict(meta, numpy=np.__version__, generator="tests/golden/make_live_golden.py")
+    data = {k: np.stack(v) if isinstance(v, list) else v for k, v in data.items()}
+    data["meta"] = np.array(json.dumps(meta))
+    np.savez_compressed(os.path.join(HERE, name + ".npz"), **data)
+
+
+def make_muw(MUW):
+    for n, seed in MUW_CASES:
+        np.random.seed(seed)
+        env = MUW(**muw_kwargs(n, seed))
+        rng = np.random.default_rng(seed)
+        rows = {}
+        for _ in range(MUW_EPISODES):
+            record(rows, reset_obs=np.array(env.reset(), np.float64))
+            for t in range(MUW_T):
+                if t % 3 == 0:
+                    acts = [rng.uniform(-10, 10, 2).astype(np.float32) for _ in range(n)]
+                else:  # goal seeking, float64 like the trainers' converted actions
+                    acts = []
+                    for a in env.agent_list:
+                        d = np.asarray(a.target_location, np.float64) - np.asarray(a.location, np.float64)
+                        dist = float(np.linalg.norm(d))
+                        acts.append(d / max(dist, 1e-9) * (min(8.0, math.sqrt(4 * dist)) if dist > 0.3 else 0.0))
+                act = np.array(acts, np.float64)
+                obs, rew, done, _ = env.step(acts, evaluate=bool(t % 7 == 0))
+                record(rows, actions=act, done=np.array(done, np.uint8), rew=np.array([float(r) for r in rew]),
+                       obs=np.array(obs, np.float64), **snap(env))
+        save(f"live_muw_n{n}_s{seed}", rows, dict(kind="live_muw", n=n, seed=seed, episodes=MUW_EPISODES, T=MUW_T,
+                                                   kwargs=muw_kwargs(n, seed)))
+
+
+def make_uw(UW):
+    for seed in UW_SEEDS:
+        np.random.seed(seed)
+        env = UW()
+        rng = np.random.default_rng(seed)
+        rows = {}
+        for _ in range(UW_EPISODES):
+            record(rows, reset_obs=np.asarray(env.reset(), np.float64))
+            for t in range(UW_T):
+                a = rng.uniform(-12, 12, 2).astype(np.float32) if (t + seed) % 2 else rng.uniform(-12, 12, 2)
+                obs, rew, done, info = env.step(a)
+                record(rows, done=np.uint8(bool(done)), rew=np.float64(rew), distance=np.float64(info["distance"]),
+                       obs=np.asarray(obs, np.float64), loc=np.asarray(env._agent_location, np.float64),
+                       vel=np.asarray(env._agent_speed, np.float64))
+        save(f"live_uw_s{seed}", rows, dict(kind="live_uw", seed=seed, episodes=UW_EPISODES, T=UW_T))
+
+
+def f64_actions(env, t):
+    acts = []
+    for a in env.agent_list:
+        d = np.asarray(a.target_location, np.float64) - np.asarray(a.location, np.float64)
+        acts.append(d * 1.5 if (t % 5 or t > 150) else d * 1.5 + np.array([0.3, -0.2]))
+    return acts
+
+
+def make_f64(MUW):
+    for n, circular in F64_CASES:
+        np.random.seed(300 + n)
+        env = MUW(num_agents=n)
+        rows = {"reset_obs": np.array(env.reset(circular=circular), np.float64)}
+        if not circular:   # the plotting script's float64 pokes (test_sac_multi_plot_trajectory.py:43-49)
+            for i in range(n):
+                theta = 2 * i * math.pi / n
+                env.agent_list[i].location = 20 * np.ones(2) * np.array([math.cos(theta), math.sin(theta)])
+                env.agent_list[i].target_location = 23 * np.ones(2) * np.array([math.cos(theta + math.pi - 0.5 * math.pi / n),
+                                                                              math.sin(theta + math.pi - 0.5 * math.pi / n)])
+            rows["poked_loc"] = np.array([a.location for a in env.agent_list], np.float64)
+            rows["poked_tgt"] = np.array([a.target_location for a in env.agent_list], np.float64)
+        for t in range(F64_T):
+            acts = f64_actions(env, t)
+            obs, rew, done, _ = env.step(acts, evaluate=bool(t % 11 == 0))
+            record(rows, actions=np.array(acts, np.float64), done=np.array(done, np.uint8),
+                   rew=np.array([float(r) for r in rew]), obs=np.array(obs, np.float64), **snap(env))
+        save(f"live_f64_n{n}_{'circular' if circular else 'poked'}", rows,
+             dict(kind="live_f64", n=n, circular=circular, T=F64_T))
+
+
+if __name__ == "__main__":
+    MUW, UW, _ = ref_loader.load()
+    make_muw(MUW)
+    make_uw(UW)
+    make_f64(MUW)

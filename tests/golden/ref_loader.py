@@ -3,9 +3,9 @@
 The reference's env arithmetic needs only numpy + math, but its modules import gym / pygame /
 cv2 / turtle at top level (MUW:3-5, AG:2-3, UW:3-7), none of which are installed here.  This
 loader registers inert placeholder modules under those names, then executes the three reference
-files from /root/reference by path.  It is used ONLY by tests/golden/make_golden.py to produce
-the committed .npz fixtures and by the optional local cross-check in tests (skipped when
-/root/reference is absent).  Nothing from the reference is copied into this repository.
+files from /root/reference by path.  It is used ONLY by tests/golden/make_golden.py and
+tests/golden/make_live_golden.py to produce the committed .npz fixtures; no test imports the
+reference.  Nothing from the reference is copied into this repository.
 """
 import importlib.util
 import os

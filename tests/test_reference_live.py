@@ -1,7 +1,7 @@
-"""Live cross-check of the oracle against the REFERENCE ITSELF, beyond the committed fixtures: fresh seeds,
-agent counts and policies every run.  Only possible where /root/reference is mounted (the build container);
-skipped on the GPU box, where the committed fixtures (tests/golden/*.npz) carry the pinning."""
-import math
+"""Cross-check of the oracle against the REFERENCE ITSELF, beyond the parity fixtures: several agent counts and seeds,
+three episodes per world, random and goal-seeking commands, evaluate flags and float64-position episodes.  The reference's
+side of every scenario is recorded in tests/golden/live_*.npz (tests/golden/make_live_golden.py drives the reference with
+exactly these scenarios); the oracle is run live here and must reproduce it bit for bit."""
 import os
 import sys
 
@@ -9,145 +9,86 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
-import ref_loader  # noqa: E402
-
-pytestmark = pytest.mark.skipif(not ref_loader.available(), reason="reference tree not mounted")
-
-
-def _snap(env):
-    ags = env.agent_list
-    return (np.array([a.location for a in ags], np.float64), np.array([a.velocity for a in ags], np.float64),
-            np.array([a.prev_distance for a in ags], np.float64),
-            np.array([(1 if a.done else 0) | (2 if a.collided else 0) for a in ags], np.uint8),
-            np.array([env.steps, env.target_reach_count, env.collision_count], np.uint32))
+from golden_util import load_fixture, tie_agents  # noqa: E402
+from make_live_golden import F64_CASES, MUW_CASES, UW_SEEDS, muw_kwargs  # noqa: E402
 
 
-@pytest.mark.parametrize("n,seed", [(1, 101), (2, 102), (3, 103), (4, 104), (4, 105), (7, 106), (12, 107), (20, 108)])
+def _check_multi_step(orc, ref, t, o_obs, o_rew, o_done, ctx, exact_rew=True):
+    np.testing.assert_array_equal(o_done[0], ref["done"][t], err_msg=ctx)
+    np.testing.assert_array_equal(orc.loc[0], ref["loc"][t], err_msg=ctx)
+    np.testing.assert_array_equal(orc.vel[0], ref["vel"][t], err_msg=ctx)
+    np.testing.assert_array_equal(orc.prev_d[0], ref["prev_d"][t], err_msg=ctx)
+    np.testing.assert_array_equal(orc.flags[0], ref["flags"][t], err_msg=ctx)
+    np.testing.assert_array_equal(orc.counters[0, :3], ref["counters"][t], err_msg=ctx)
+    if exact_rew:
+        np.testing.assert_array_equal(o_rew[0], ref["rew"][t], err_msg=ctx)
+    else:
+        np.testing.assert_allclose(o_rew[0], ref["rew"][t], rtol=1e-6, atol=1e-6, err_msg=ctx)
+
+
+@pytest.mark.parametrize("n,seed", MUW_CASES)
 def test_oracle_equals_live_reference(oracle_mod, n, seed):
-    MUW, _, _ = ref_loader.load()
-    np.random.seed(seed)
-    kw = dict(num_agents=n) if seed % 2 else dict(num_agents=n, x_size=30.0, y_size=36.0, d_sense=9, collider_radius=0.8)
-    env = MUW(**kw)
-    orc = oracle_mod.OracleMulti(num_envs=1, **kw)
+    ref, meta = load_fixture(f"live_muw_n{n}_s{seed}")
+    assert meta["kwargs"] == muw_kwargs(n, seed)
+    orc = oracle_mod.OracleMulti(num_envs=1, **muw_kwargs(n, seed))
     g = oracle_mod.MTStream(seed)
-    rng = np.random.default_rng(seed)
-    for episode in range(3):
-        obs_ref = env.reset()
+    T = meta["T"]
+    for episode in range(meta["episodes"]):
         orc.reset_mt(g)
-        np.testing.assert_array_equal(orc.observe()[0], np.array(obs_ref))
-        for t in range(150):
-            if t % 3 == 0:
-                acts = [rng.uniform(-10, 10, 2).astype(np.float32) for _ in range(n)]
-            else:  # goal seeking, float64 like the trainers' converted actions
-                acts = []
-                for a in env.agent_list:
-                    d = np.asarray(a.target_location, np.float64) - np.asarray(a.location, np.float64)
-                    dist = float(np.linalg.norm(d))
-                    acts.append(d / max(dist, 1e-9) * (min(8.0, math.sqrt(4 * dist)) if dist > 0.3 else 0.0))
-            ev = bool(t % 7 == 0)
-            obs, rew, done, _ = env.step(acts, evaluate=ev)
-            o_obs, o_rew, o_done = orc.step(np.array(acts, np.float64), evaluate=ev)
-            loc, vel, pd, flags, cnt = _snap(env)
+        np.testing.assert_array_equal(orc.observe()[0], ref["reset_obs"][episode])
+        for t in range(T):
+            k = episode * T + t
+            o_obs, o_rew, o_done = orc.step(ref["actions"][k], evaluate=bool(t % 7 == 0))
             ctx = f"n={n} seed={seed} ep={episode} t={t}"
-            np.testing.assert_array_equal(o_done[0], np.array(done, np.uint8), err_msg=ctx)
-            np.testing.assert_array_equal(orc.loc[0], loc, err_msg=ctx)
-            np.testing.assert_array_equal(orc.vel[0], vel, err_msg=ctx)
-            np.testing.assert_array_equal(orc.prev_d[0], pd, err_msg=ctx)
-            np.testing.assert_array_equal(orc.flags[0], flags, err_msg=ctx)
-            np.testing.assert_array_equal(orc.counters[0, :3], cnt, err_msg=ctx)
-            np.testing.assert_array_equal(o_rew[0], np.array([float(r) for r in rew]), err_msg=ctx)
-            np.testing.assert_array_equal(o_obs[0], np.array(obs), err_msg=ctx)
+            _check_multi_step(orc, ref, k, o_obs, o_rew, o_done, ctx)
+            np.testing.assert_array_equal(o_obs[0], ref["obs"][k], err_msg=ctx)
 
 
-@pytest.mark.parametrize("seed", [201, 202])
+@pytest.mark.parametrize("seed", UW_SEEDS)
 def test_oracle_uw_equals_live_reference(oracle_mod, seed):
-    _, UW, _ = ref_loader.load()
-    np.random.seed(seed)
-    env = UW()
+    ref, meta = load_fixture(f"live_uw_s{seed}")
     orc = oracle_mod.OracleSingle(num_envs=1)
     g = oracle_mod.MTStream(seed)
     rng = np.random.default_rng(seed)
-    for episode in range(3):
-        obs_ref = env.reset()
+    T = meta["T"]
+    for episode in range(meta["episodes"]):
         orc.reset_mt(g)
-        np.testing.assert_array_equal(orc.observe()[0], obs_ref)
-        for t in range(200):
+        np.testing.assert_array_equal(orc.observe()[0], ref["reset_obs"][episode])
+        for t in range(T):
+            k = episode * T + t
             a = rng.uniform(-12, 12, 2).astype(np.float32) if (t + seed) % 2 else rng.uniform(-12, 12, 2)
-            obs, rew, done, info = env.step(a)
             o_obs, o_rew, o_done, o_info = orc.step(a)
-            assert bool(o_done[0]) == bool(done) and o_rew[0] == float(rew) and o_info[0] == float(info["distance"])
-            np.testing.assert_array_equal(o_obs[0], obs)
-            np.testing.assert_array_equal(orc.loc[0], np.asarray(env._agent_location, np.float64))
-            np.testing.assert_array_equal(orc.vel[0], np.asarray(env._agent_speed, np.float64))
+            assert bool(o_done[0]) == bool(ref["done"][k]) and o_rew[0] == ref["rew"][k] and o_info[0] == ref["distance"][k]
+            np.testing.assert_array_equal(o_obs[0], ref["obs"][k])
+            np.testing.assert_array_equal(orc.loc[0], ref["loc"][k])
+            np.testing.assert_array_equal(orc.vel[0], ref["vel"][k])
 
 
-def test_committed_fixture_regenerates_identically():
-    """The committed .npz really is what the reference produces here (one fixture re-generated in memory)."""
-    from golden_util import load_fixture
-    data, meta = load_fixture("multi_random_n4_s2")
-    MUW, _, _ = ref_loader.load()
-    np.random.seed(meta["np_seed"])
-    env = MUW(num_agents=4)
-    env.reset()
-    rng = np.random.default_rng(2)
-    for t in range(60):
-        acts = [rng.uniform(-10, 10, size=2).astype(np.float32) for _ in range(4)]
-        np.testing.assert_array_equal(np.array(acts), data["actions"][t])
-        obs, rew, done, _ = env.step(acts)
-        np.testing.assert_array_equal(np.array(obs), data["obs"][t])
-        np.testing.assert_array_equal(np.array([float(r) for r in rew]), data["rew"][t])
-
-
-@pytest.mark.parametrize("n,circular", [(4, True), (6, True), (5, False), (3, False)])
+@pytest.mark.parametrize("n,circular", F64_CASES)
 def test_oracle_float64_episodes_equal_live_reference(oracle_mod, n, circular):
-    """Float64-position episodes of the live reference: reset(circular=True) (MUW:157-163), and a random reset
+    """Float64-position episodes of the reference: reset(circular=True) (MUW:157-163), and a random reset
     followed by the plotting script's float64 pokes of location / target_location
     (test_sac_multi_plot_trajectory.py:43-49; init / prev distance stay the stale float32 scalars).  State and masks
     bit for bit; in the poke pattern the reward may differ in the last float32 digit (NEP 50 evaluates
     1.5*np.float32(init_distance) in float32 there; the oracle keeps no scalar dtypes)."""
-    MUW, _, _ = ref_loader.load()
-    np.random.seed(300 + n)
-    env = MUW(num_agents=n)
+    ref, meta = load_fixture(f"live_f64_n{n}_{'circular' if circular else 'poked'}")
     orc = oracle_mod.OracleMulti(num_envs=1, num_agents=n)
     g = oracle_mod.MTStream(300 + n)
-    obs_ref = env.reset(circular=circular)
     orc.reset_mt(g, circular=circular)
     if not circular:
-        for i in range(n):
-            theta = 2 * i * math.pi / n
-            env.agent_list[i].location = 20 * np.ones(2) * np.array([math.cos(theta), math.sin(theta)])
-            env.agent_list[i].target_location = 23 * np.ones(2) * np.array([math.cos(theta + math.pi - 0.5 * math.pi / n),
-                                                                          math.sin(theta + math.pi - 0.5 * math.pi / n)])
-            orc.loc[0, i] = env.agent_list[i].location
-            orc.tgt[0, i] = env.agent_list[i].target_location
+        orc.loc[0] = ref["poked_loc"]
+        orc.tgt[0] = ref["poked_tgt"]
         orc.f64pos[:] = 1
     else:
-        np.testing.assert_array_equal(orc.observe()[0], np.array(obs_ref))
+        np.testing.assert_array_equal(orc.observe()[0], ref["reset_obs"])
     assert int(orc.f64pos[0]) == 1
-    for t in range(900):
-        acts = []
-        for a in env.agent_list:
-            d = np.asarray(a.target_location, np.float64) - np.asarray(a.location, np.float64)
-            acts.append(d * 1.5 if (t % 5 or t > 150) else d * 1.5 + np.array([0.3, -0.2]))
-        obs, rew, done, _ = env.step(acts, evaluate=bool(t % 11 == 0))
-        o_obs, o_rew, o_done = orc.step(np.array(acts, np.float64), evaluate=bool(t % 11 == 0))
-        loc, vel, pd, flags, cnt = _snap(env)
+    for t in range(meta["T"]):
+        o_obs, o_rew, o_done = orc.step(ref["actions"][t], evaluate=bool(t % 11 == 0))
         ctx = f"n={n} circular={circular} t={t}"
-        np.testing.assert_array_equal(o_done[0], np.array(done, np.uint8), err_msg=ctx)
-        np.testing.assert_array_equal(orc.loc[0], loc, err_msg=ctx)
-        np.testing.assert_array_equal(orc.vel[0], vel, err_msg=ctx)
-        np.testing.assert_array_equal(orc.prev_d[0], pd, err_msg=ctx)
-        np.testing.assert_array_equal(orc.flags[0], flags, err_msg=ctx)
-        np.testing.assert_array_equal(orc.counters[0, :3], cnt, err_msg=ctx)
-        ref_rew = np.array([float(r) for r in rew])
-        if circular:
-            np.testing.assert_array_equal(o_rew[0], ref_rew, err_msg=ctx)
-        else:
-            np.testing.assert_allclose(o_rew[0], ref_rew, rtol=1e-6, atol=1e-6, err_msg=ctx)
+        _check_multi_step(orc, ref, t, o_obs, o_rew, o_done, ctx, exact_rew=circular)
         # neighbour columns of exactly tied agents depend on numpy's argsort tie order (platform dependent)
-        from golden_util import tie_agents
-        ties = tie_agents(loc, 15, True)
-        got, want = o_obs[0].copy(), np.array(obs)
+        ties = tie_agents(ref["loc"][t], 15, True)
+        got, want = o_obs[0].copy(), ref["obs"][t].copy()
         got[ties, 4:] = 0; want[ties, 4:] = 0
         np.testing.assert_array_equal(got, want, err_msg=ctx)
     assert int(orc.counters[0, 1]) > 0, "nobody reached a target: scenario too short"
