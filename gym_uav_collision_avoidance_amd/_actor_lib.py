@@ -1,0 +1,109 @@
+"""ctypes binding of libuavx_actor.so (include/uavx_actor.h), the fused actor-inference kernels.  Built, checked for
+staleness and loaded like libuavx.so (_lib.py), from a directory of its own so that the environment library and the
+source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device raises."""
+import ctypes
+import os
+import subprocess
+
+from . import _lib
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+CSRC = os.path.join(_HERE, "actor_csrc")
+HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_actor.h")
+LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
+ABI_VERSION = 1
+
+SAC, TD3, DDPG = 0, 1, 2
+F32, BF16 = 0, 1
+RAW, DETERMINISTIC, SAC_SAMPLE, ADD_CLAMP = 0, 1, 2, 3
+OK, ERR_INVALID_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_PACKED = 0, -1, -2, -3, -4
+
+# every symbol include/uavx_actor.h declares (tests check the built library exports each of them)
+SYMBOLS = ("uavx_actor_version", "uavx_actor_strerror", "uavx_actor_create", "uavx_actor_destroy", "uavx_actor_pack",
+           "uavx_actor_forward")
+
+_lib_handle = None
+
+
+def _sources():
+    import glob
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))) + [HEADER]
+
+
+def source_hash():
+    """sha256 over the code (comments and whitespace dropped, _lib._code_only) of actor_csrc/*.hip, *.hpp and
+    include/uavx_actor.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override; 16 hex digits."""
+    import hashlib
+    h = hashlib.sha256()
+    for f in _sources():
+        h.update(os.path.basename(f).encode())
+        h.update(_lib._code_only(open(f, "r", encoding="utf-8", errors="replace").read()).encode())
+    mk = open(os.path.join(CSRC, "Makefile"), "r", encoding="utf-8", errors="replace").read()
+    mk = "\n".join(l.split("#", 1)[0].rstrip() for l in mk.splitlines() if l.split("#", 1)[0].strip())
+    env = ";".join(f"{k}={os.environ[k]}" for k in ("HIPCC", "ARCH", "HIPFLAGS") if k in os.environ)
+    h.update(b"Makefile")
+    h.update((mk + "\n" + env).encode())
+    return h.hexdigest()[:16]
+
+
+def build(force=False):
+    """hipcc build of actor_csrc/ into libuavx_actor.so (gfx950; cross-compiles without a GPU), under an exclusive file
+    lock into a temporary name renamed into place, as _lib.build does."""
+    import fcntl
+    with open(os.path.join(CSRC, ".build.lock"), "w") as lock:
+        fcntl.flock(lock, fcntl.LOCK_EX)
+        try:
+            if not force and os.path.exists(LIB_PATH) and _up_to_date():
+                return LIB_PATH
+            tmp = f"libuavx_actor.so.tmp{os.getpid()}"
+            proc = subprocess.run(["make", "-C", CSRC, "-B", f"OUT={tmp}", f"SRCHASH={source_hash()}"], stdout=subprocess.PIPE,
+                                  stderr=subprocess.STDOUT, text=True)
+            if proc.returncode != 0:
+                try:
+                    os.unlink(os.path.join(CSRC, tmp))
+                except OSError:
+                    pass
+                raise RuntimeError(f"uavx: building {LIB_PATH} failed (make exit {proc.returncode}):\n{proc.stdout[-4000:]}")
+            os.replace(os.path.join(CSRC, tmp), LIB_PATH)
+        finally:
+            fcntl.flock(lock, fcntl.LOCK_UN)
+    return LIB_PATH
+
+
+def _up_to_date():
+    """Does LIB_PATH carry the hash of the sources in the tree (read from the file, not through dlopen)?"""
+    import re
+    with open(LIB_PATH, "rb") as f:
+        mark = re.search(rb"UAVX_ACTOR_SRC_HASH=([0-9a-f]*)\0", f.read())
+    if mark is None:
+        return False
+    if mark.group(1):
+        return mark.group(1).decode() == source_hash()
+    return os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in _sources() + [os.path.join(CSRC, "Makefile")])
+
+
+def load():
+    global _lib_handle
+    if _lib_handle is not None:
+        return _lib_handle
+    if not os.path.exists(LIB_PATH) or not _up_to_date():
+        build()                 # a build, not a fallback: a compile error is raised as such
+    L = ctypes.CDLL(LIB_PATH)
+    vp, i64, i32, f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
+    L.uavx_actor_version.restype = i32
+    if L.uavx_actor_version() != ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks actor ABI version {L.uavx_actor_version()}, this package binds {ABI_VERSION}: "
+                           f"rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_actor_strerror.restype = ctypes.c_char_p
+    L.uavx_actor_strerror.argtypes = [i32]
+    L.uavx_actor_create.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.uavx_actor_destroy.argtypes = [vp]
+    L.uavx_actor_pack.argtypes = [vp] + [vp] * 8 + [vp]
+    L.uavx_actor_forward.argtypes = [vp, vp, i64, i64, vp, f32, i32, vp, i64, vp]
+    _lib_handle = L
+    return L
+
+
+def check(rc, what):
+    if rc != OK:
+        raise RuntimeError(f"uavx: {what} failed: {load().uavx_actor_strerror(rc).decode()} ({rc})")

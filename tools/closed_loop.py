@@ -20,6 +20,7 @@ sys.path.insert(0, ROOT)
 from gym_uav_collision_avoidance_amd import BatchedMultiUAVWorld2D, _lib      # noqa: E402
 from gym_uav_collision_avoidance_amd.policy import DDPGActor, GaussianPolicy, TD3Actor   # noqa: E402
 from gym_uav_collision_avoidance_amd.replay import DeviceReplay               # noqa: E402
+from gym_uav_collision_avoidance_amd.fused_actor import FusedActor           # noqa: E402
 
 dev = torch.device("cuda", 0)
 RING = 8           # ring slots = steps per graph (the slot indices of a pass repeat, so one graph serves every pass)
@@ -54,7 +55,9 @@ def time_graph(g, steps_per_replay, replays=60):
     return sorted(ts)[1] * 1e6
 
 
-def workload(name, E, N, B, curriculum, actor, dtype=torch.float32):
+def workload(name, E, N, B, curriculum, actor, dtype=torch.float32, fused=None):
+    """fused: None = the torch module (actor_dtype = its dtype); "f32" / "bf16" = FusedActor of the float32 module, writing the
+    action slot in place (actor_impl "fused", actor_dtype = the kernel's precision)."""
     kw = dict(num_bodies=B) if B else {}
     env = BatchedMultiUAVWorld2D(E, num_agents=N, device=dev, seed=0, **kw)
     if curriculum:
@@ -64,12 +67,16 @@ def workload(name, E, N, B, curriculum, actor, dtype=torch.float32):
     mem = DeviceReplay(env, horizon=RING - 1)
     mem.begin(env.reset())
     pol = actor().to(dev).to(dtype).eval()          # bfloat16: the matrix cores' native input type (the env stays float32 / float64)
+    fa = FusedActor.from_module(pol, precision=fused) if fused else None
     gen = torch.Generator(device=dev).manual_seed(0)
 
     def loop_pass():                      # RING steps of the closed loop
         with torch.no_grad():
             for _ in range(RING):
-                mem.action_slot().copy_(pol.act(mem.state.to(dtype)))     # (copy_ converts back to the ring's float32)
+                if fa is not None:
+                    fa.act(mem.state, out=mem.action_slot())
+                else:
+                    mem.action_slot().copy_(pol.act(mem.state.to(dtype)))     # (copy_ converts back to the ring's float32)
                 mem.step(**STEP_KW)
 
     def env_pass():                       # the same launches fed by whatever sits in the action slots
@@ -82,13 +89,18 @@ def workload(name, E, N, B, curriculum, actor, dtype=torch.float32):
     def actor_pass():
         with torch.no_grad():
             for _ in range(RING):
-                out_rows.copy_(pol.act(obs_rows))
+                if fa is not None:
+                    fa.act(obs_rows, out=out_rows)
+                else:
+                    out_rows.copy_(pol.act(obs_rows))
 
     for _ in range(40):                   # parked layouts in place, caches warm
         loop_pass()
     res = dict(workload=name, envs=E, learners=N, bodies=B, curriculum_levels=4 if curriculum else 0, actor=actor.__name__,
                actor_dtype=str(dtype).replace("torch.", ""),
                actor_rows_per_step=E * N, ring_slots=RING)
+    if fa is not None:
+        res.update(actor_impl="fused", actor_dtype=fused)
     res["loop_us_per_step"] = time_graph(graph_of(loop_pass), RING)
     res["env_launch_us_per_step"] = time_graph(graph_of(env_pass), RING)
     res["actor_us_per_step"] = time_graph(graph_of(actor_pass), RING)
@@ -113,10 +125,18 @@ if __name__ == "__main__":
     for dt in (torch.float32, torch.bfloat16):
         rows.append(workload("BASELINE configs[4]: 65 536 envs x (8 UAVs + 16 scripted bodies), 4-level curriculum", args.envs, 8, 16, True, GaussianPolicy, dt))
         print(json.dumps(rows[-1]), flush=True)
+    for fused in ("f32", "bf16"):        # the fused HIP actor (libuavx_actor.so) beside the torch rows above
+        for actor in (GaussianPolicy, TD3Actor, DDPGActor):
+            rows.append(workload("BASELINE configs[2]: 65 536 envs x 4 UAVs", args.envs, 4, 0, False, actor, fused=fused))
+            print(json.dumps(rows[-1]), flush=True)
+            rows.append(workload("BASELINE configs[4]: 65 536 envs x (8 UAVs + 16 scripted bodies), 4-level curriculum", args.envs, 8,
+                                 16, True, actor, fused=fused))
+            print(json.dumps(rows[-1]), flush=True)
+    from gym_uav_collision_avoidance_amd import _actor_lib
     doc = dict(what="closed rollout loop (batched actor forward -> replay action slot -> fused uavx_step_ex into the replay ring) captured "
                     "as one hipGraph per ring pass; random-initialised actors of the reference's architectures (no checkpoint ships with "
                     "the reference); the reference prints the same quantity for its host loop as 'Steps Per Sec' (test_sac_multi.py:120-123)",
-               device=torch.cuda.get_device_name(0), csrc_sha=_lib.source_hash(), torch=torch.__version__, rows=rows)
+               device=torch.cuda.get_device_name(0), csrc_sha=_lib.source_hash(), actor_sha=_actor_lib.source_hash(), torch=torch.__version__, rows=rows)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     json.dump(doc, open(args.out, "w"), indent=1)
     print("wrote", args.out)
