@@ -19,7 +19,7 @@ F32, F64 = 0, 1
 
 # every symbol include/uavx.h declares (tests check the built library exports each of them)
 SYMBOLS = (
-    "uavx_version", "uavx_build_info", "uavx_selftest", "uavx_strerror", "uavx_create", "uavx_destroy", "uavx_last_error", "uavx_num_envs",
+    "uavx_version", "uavx_build_info", "uavx_selftest", "uavx_polar_commands", "uavx_strerror", "uavx_create", "uavx_destroy", "uavx_last_error", "uavx_num_envs",
     "uavx_num_agents", "uavx_set_config", "uavx_set_body_rule", "uavx_num_bodies", "uavx_get_bodies", "uavx_set_bodies",
     "uavx_set_curriculum", "uavx_set_env_levels", "uavx_get_env_levels", "uavx_set_prefetch", "uavx_reset", "uavx_step", "uavx_step_k", "uavx_observe", "uavx_get_state",
     "uavx_set_state", "uavx_set_position_mode", "uavx_get_position_mode", "uavx_set_state_f64", "uavx_get_state_f64",
@@ -65,7 +65,18 @@ class StateViewF64(ctypes.Structure):  # uavx_state_view_f64
 
 POS_F32, POS_F64 = 0, 1
 
-ACTION_CARTESIAN, ACTION_POLAR = 0, 1
+ACTION_CARTESIAN, ACTION_POLAR, ACTION_POLAR_REFERENCE = 0, 1, 2
+
+
+def action_mode(polar):
+    """step_ex's `polar` option -> uavx_action_mode: False (velocity commands), True (float32 sincospi conversion, the
+    cheapest launch) or "reference" (the trainers' expression with their dtypes, bit for bit)."""
+    if isinstance(polar, str):
+        if polar == "reference":
+            return ACTION_POLAR_REFERENCE
+    elif polar is None or polar in (False, True):   # (bool, 0 / 1, numpy bools: what the flag always took)
+        return ACTION_POLAR if polar else ACTION_CARTESIAN
+    raise ValueError(f"uavx: polar must be False, True or \"reference\", not {polar!r}")
 RESET_NEVER, RESET_AGENT0_DONE, RESET_ALL_DONE = 0, 1, 2
 
 
@@ -233,6 +244,7 @@ def load():
                            f"rebuild it (`make -B -C {CSRC}`)")
     L.uavx_build_info.restype = ctypes.c_char_p      # (exists from ABI version 3 on: bound behind the version check)
     L.uavx_selftest.argtypes = [i32, ctypes.POINTER(ctypes.c_uint64)]
+    L.uavx_polar_commands.argtypes = [vp, i32, i64, ctypes.c_float, vp, vp]
     L.uavx_strerror.restype = ctypes.c_char_p
     L.uavx_strerror.argtypes = [i32]
     L.uavx_create.argtypes = [ctypes.POINTER(Config), i64, i64, i32, ctypes.POINTER(vp)]

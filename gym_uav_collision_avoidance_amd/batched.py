@@ -336,6 +336,9 @@ class BatchedMultiUAVWorld2D(_Base):
                 out=None, flags_out=None, packed_flags=False):
         """env.step plus what the reference's trainer loops do around it, in the same launch:
           polar=True       actions are policy outputs a in [-1,1]^2, converted like test_sac_multi.py:77-80
+                           (float32 arithmetic, within 4e-6 of the trainers' command: the cheapest launch)
+          polar="reference" the same conversion as the trainers compute it (NumPy 2 dtypes): float32 actions give the
+                           trainers' float32 command bit for bit, float64 actions a float64 command
           auto_reset       "agent0_done" (test_sac_multi.py:112) / "all_done" (:116,161) / None; step_cap (:17,67)
           track_returns    accumulate episode return / evaluation score per env (:106,157)
         Auto-reset is next-step: an ended env keeps its terminal observation in this call's outputs and
@@ -395,7 +398,7 @@ class BatchedMultiUAVWorld2D(_Base):
         else:
             args.reset_mask, args.ended, args.truncated = self._flag_ptrs
         args.actions, args.action_dtype = a.data_ptr(), code
-        args.action_mode = _lib.ACTION_POLAR if polar else _lib.ACTION_CARTESIAN
+        args.action_mode = _lib.action_mode(polar)
         args.evaluate = 1 if evaluate else 0
         args.reset_policy = self._POLICIES[auto_reset]
         args.step_cap, args.track_returns, args.seed = int(step_cap), 1 if track_returns else 0, self.seed
@@ -698,7 +701,8 @@ class BatchedUAVWorld2D(_Base):
 
     def step_ex(self, actions, polar=False, auto_reset=False, step_cap=0, track_returns=True):
         """env.step plus the single-agent trainer loop's bookkeeping (test_sac.py:77-80,98,106-109): polar=True
-        converts policy outputs a in [-1,1]^2 (v = (a0/2+0.5)*action_space.high[0], theta = a1*pi); auto_reset
+        converts policy outputs a in [-1,1]^2 (v = (a0/2+0.5)*action_space.high[0], theta = a1*pi; polar="reference": with the
+        trainer's dtypes, bit for bit, as in BatchedMultiUAVWorld2D.step_ex); auto_reset
         re-initialises an env in the call AFTER the one that returned done (info["reset_mask"]); episode returns
         and lengths are accumulated per env (episode_stats())."""
         if (type(actions) is torch.Tensor and actions.shape == self._act_shape and actions.dtype in _TORCH_DT
@@ -721,7 +725,7 @@ class BatchedUAVWorld2D(_Base):
         f = self._flip
         args = self._ex_args[f]
         args.actions, args.action_dtype = a.data_ptr(), code
-        args.action_mode = _lib.ACTION_POLAR if polar else _lib.ACTION_CARTESIAN
+        args.action_mode = _lib.action_mode(polar)
         args.auto_reset, args.step_cap, args.track_returns, args.seed = (1 if auto_reset else 0), int(step_cap), (1 if track_returns else 0), self.seed
         rc = self._ex_fn(self._h, self._ex_refs[f], self._stream())
         if rc:

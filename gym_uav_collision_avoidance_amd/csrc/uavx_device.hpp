@@ -223,6 +223,84 @@ __device__ __forceinline__ void sincospi32(float t, float &sn, float &cs) {
     cs = (q == 0) ? pc : (q == 1) ? -ps : (q == 2) ? -pc : ps;
 }
 
+// sin and cos in double for the reference polar conversion (below): fdlibm's algorithm (e_rem_pio2 medium-size Cody-Waite
+// reduction by pi/2 in three 33-bit parts, k_sin / k_cos polynomials on [-pi/4, pi/4] with the reduced argument as a
+// double-double), error below 1 ulp -- what glibc's sin / cos promise, with neither a table nor a call.  |x| < 2^-27 returns
+// (x, 1) as fdlibm does (keeps the sign of a zero).  Past |x| = 2^19 pi/2 (|a1| > 2.6e5, far outside the action box) the
+// reduction would lose bits: those lanes take the library's sincos in a branch no action in [-1, 1] reaches.  NaN / +-inf give NaN.
+__device__ __forceinline__ void sincos_ref(double x, double &sn, double &cs) {
+    const double ax = fabs(x);
+    if (__builtin_expect(__any(ax > 823549.6561538912), 0)) {   // 2^19 * pi/2 (cold: every action in [-1, 1] has |x| <= pi)
+        if (ax > 823549.6561538912) { sincos(x, &sn, &cs); return; }
+    }
+    const double fn = rint(x * 6.36619772367581382433e-01);     // invpio2
+    const int n = (int)fn;
+    // e_rem_pio2 with the second and third iteration always taken (fdlibm skips them when they change nothing)
+    double r = x - fn * 1.57079632673412561417e+00;              // pio2_1: 33 bits, fn * pio2_1 exact
+    double t = r;                                                // (the first iteration's tail pio2_1t = pio2_2 + pio2_2t)
+    double w = fn * 6.07710050630396597660e-11;                  // pio2_2
+    r = t - w;
+    w = fn * 2.02226624879595063154e-21 - ((t - r) - w);         // pio2_2t
+    t = r;
+    w = fn * 2.02226624871116645580e-21;                         // pio2_3
+    r = t - w;
+    w = fn * 8.47842766036889956997e-32 - ((t - r) - w);         // pio2_3t
+    const double y0 = r - w;
+    const double y1 = (r - y0) - w;
+    // k_sin(y0, y1)
+    const double z = y0 * y0, zz = z * z, v = z * y0;
+    const double rs = 8.33333333332248946124e-03 + z * (-1.98412698298579493134e-04 + z * 2.75573137070700676789e-06) +
+                      z * zz * (-2.50507602534068634195e-08 + z * 1.58969099521155010221e-10);
+    const double ks = y0 - ((z * (0.5 * y1 - v * rs) - y1) - v * -1.66666666666666324348e-01);
+    // k_cos(y0, y1)
+    const double rc = z * (4.16666666666666019037e-02 + z * (-1.38888888888741095749e-03 + z * 2.48015872894767294178e-05)) +
+                      zz * zz * (-2.75573143513906633035e-07 + z * (2.08757232129817482790e-09 + z * -1.13596475577881948265e-11));
+    const double hz = 0.5 * z, wc = 1.0 - hz;
+    const double kc = wc + (((1.0 - wc) - hz) + (z * rc - y0 * y1));
+    const int q = n & 3;
+    double s_ = (q == 0) ? ks : (q == 1) ? kc : (q == 2) ? -ks : -kc;
+    double c_ = (q == 0) ? kc : (q == 1) ? -ks : (q == 2) ? -kc : ks;
+    const bool tiny = ax < 7.450580596923828125e-9;              // 2^-27
+    s_ = tiny ? x : s_;
+    c_ = tiny ? 1.0 : c_;
+    const bool fin = ax <= 1.7976931348623157e308;               // NaN / inf: NaN
+    sn = fin ? s_ : __builtin_nan("");
+    cs = fin ? c_ : __builtin_nan("");
+}
+
+// UAVX_ACTION_POLAR_REFERENCE: the trainers' own expression (test_sac_multi.py:77-80, test_sac.py:77-78) with the dtypes it
+// has under NumPy 2 (NEP 50).  `h` is the float32 speed scale: ||action_space.high|| (MUW) or action_space.high[0] (UW).
+// float32 action (the policy branch): v = fl32(fl32(a0/2 + 0.5f) * h), theta = fl32(a1 * fl32(pi)), the Python float
+// math.cos / math.sin of the widened theta rounded to float32 (np.float32 * Python float), and a FLOAT32 command
+// (fl32(v*c), fl32(v*s)).  Every step is one correctly rounded operation (compiled without contraction), so the result is the
+// reference's bit for bit whenever the double cos / sin round to the same float32 as glibc's -- all but values within
+// ~2^-52 of a float32 rounding midpoint.  a0/2 is computed as a0*0.5f: the same correctly rounded value, subnormals included.
+// A NaN or infinite theta gives a NaN command (the reference returns NaN for NaN and raises for +-inf).
+__device__ __forceinline__ void polar_to_command_ref32(float a0, float a1, float h, double &ax, double &ay) {
+    const float u = a0 * 0.5f + 0.5f;
+    const float v = u * h;
+    const float theta = a1 * 3.14159265358979323846f;
+    double s, c;
+    sincos_ref((double)theta, s, c);
+    ax = (double)(v * (float)c);
+    ay = (double)(v * (float)s);
+}
+// float64 action (the warm-up branch, np.random.uniform): every step in double, a FLOAT64 command.  sincos_ref and glibc are
+// both within 1 ulp of the true value, so the command may differ from the reference's by an ulp (rate).
+__device__ __forceinline__ void polar_to_command_ref64(double a0, double a1, float h, double &ax, double &ay) {
+    const double v = (a0 * 0.5 + 0.5) * (double)h;
+    const double theta = a1 * 3.14159265358979323846;
+    double s, c;
+    sincos_ref(theta, s, c);
+    ax = v * c;
+    ay = v * s;
+}
+template <bool ACT64>
+__device__ __forceinline__ void polar_to_command_ref(float h, double &ax, double &ay) {
+    if (ACT64) polar_to_command_ref64(ax, ay, h, ax, ay);
+    else polar_to_command_ref32((float)ax, (float)ay, h, ax, ay);   // ax, ay hold a widened float32 action: exact
+}
+
 // Philox4x32-10, counter-based: one call yields the two 53-bit uniforms of one
 // np.random.uniform(lo, hi, (2,)) draw (MUW:126,131,144; UW:121-126).
 __device__ __forceinline__ void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,

@@ -198,67 +198,16 @@ __device__ __forceinline__ void uw_fold(const UwParams &p, int64_t e, uint32_t s
     }
 }
 
-// uavx_uw_step_ex: step + polar conversion + next-step auto-reset + episode statistics.
-template <bool ACT64>
-__global__ __launch_bounds__(kBlock) void uw_step_ex_kernel(UwParams p, UwExtra x, const void *__restrict__ actions,
-                                                            float4 *__restrict__ obs_out, float *__restrict__ rew_out,
-                                                            uint8_t *__restrict__ done_out, float *__restrict__ info_out) {
-    const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    const bool live = e < p.E;
-    const uint32_t wave_count = p.wave_steps[blockIdx.x];
-    if (live) {
-        const uint4 rec = p.rec[e];
-        uint32_t steps = wave_count - rec.x;
-        UwRegs s;
-        if (rec.y & kUwPending) {  // the env starts a new episode instead of stepping
-            const uint32_t episode = rec.y & ~kUwPending;
-            uw_fold(p, e, steps, (p.goal[e].flags & kUwReached) != 0, __uint_as_float(rec.z));
-            uw_draw_episode(p, e, episode, x.seed_lo, x.seed_hi, s);
-            uw_store_fresh(p, e, s);
-            p.rec[e] = make_uint4(wave_count + 1u, episode + 1u, 0u, 0u);   // UW:131 steps = 0 after this launch
-            const float tdx = s.tx - s.x, tdy = s.ty - s.y;
-            const float theta = atan2_fast((float)s.vy, (float)s.vx);
-            obs_out[e] = uw_obs(p, norm32((float)s.vx, (float)s.vy), theta, s.init_d, wrap_pi(atan2_fast(tdy, tdx) - theta));
-            rew_out[e] = 0.f;
-            done_out[e] = 0;
-            if (info_out) info_out[e] = s.init_d;
-            if (x.reset_mask) x.reset_mask[e] = 1;
-            if (x.ended) x.ended[e] = 0;
-            if (x.truncated) x.truncated[e] = 0;
-        } else {
-            double ax, ay;
-            uw_load_action<ACT64>(actions, e, ax, ay);
-            uw_load(p, e, s);
-            const uint32_t flags_in = s.flags;
-            bool act_f32 = !ACT64;
-            if (x.action_mode == UAVX_ACTION_POLAR) {  // test_sac.py:77-80 in float32
-                const float v = fmaf((float)ax, 0.5f, 0.5f) * p.high0;
-                float sn, cs;
-                sincospi32((float)ay, sn, cs);
-                ax = (double)(v * cs); ay = (double)(v * sn);
-                act_f32 = true;
-            }
-            float4 obs; float rew, dist; uint32_t dn;
-            uw_step_env(p, s, ax, ay, act_f32, obs, rew, dn, dist);
-            obs_out[e] = obs;
-            rew_out[e] = rew;
-            done_out[e] = (uint8_t)dn;
-            if (info_out) info_out[e] = dist;
-            uw_store(p, e, s, flags_in);
-            steps += 1;                                                      // UW:170
-            const bool terminal = x.auto_reset && dn;                                 // test_sac.py:106-109
-            const bool ended = terminal || (x.step_cap != 0 && steps >= x.step_cap);   // :17
-            if (x.ended) x.ended[e] = ended ? 1 : 0;
-            if (x.truncated) x.truncated[e] = (ended && !terminal) ? 1 : 0;
-            uint4 out = rec;
-            out.y = (rec.y & ~kUwPending) | (ended ? kUwPending : 0u);
-            if (x.track_returns) out.z = __float_as_uint(__uint_as_float(rec.z) + rew);   // test_sac.py:98
-            if (out.y != rec.y || out.z != rec.z) p.rec[e] = out;
-            if (x.reset_mask) x.reset_mask[e] = 0;
-        }
-    }
-    if (threadIdx.x == 0) p.wave_steps[blockIdx.x] = wave_count + 1u;   // single writer: this wavefront
-}
+#define UAVX_EX_KERNEL uw_step_ex_kernel
+#define UAVX_EX_REF false
+#include "uavx_uw_step_ex.hpp"
+#undef UAVX_EX_KERNEL
+#undef UAVX_EX_REF
+#define UAVX_EX_KERNEL uw_step_ex_ref_kernel
+#define UAVX_EX_REF true
+#include "uavx_uw_step_ex.hpp"
+#undef UAVX_EX_KERNEL
+#undef UAVX_EX_REF
 
 __global__ __launch_bounds__(kBlock) void uw_episode_stats_kernel(UwParams p, uint32_t *counts, float *returns, int clear) {
     const int64_t e = (int64_t)blockIdx.x * kBlock + threadIdx.x;
@@ -516,7 +465,8 @@ int uavx_uw_step_ex(uavx_uw_handle *h, const uavx_uw_step_args *a, void *stream)
     if (!a->actions || !a->obs || !a->rew || !a->done) return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: NULL buffer");
     if (a->action_dtype != UAVX_F32 && a->action_dtype != UAVX_F64)
         return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: action_dtype must be UAVX_F32 or UAVX_F64");
-    if (a->action_mode != UAVX_ACTION_CARTESIAN && a->action_mode != UAVX_ACTION_POLAR)
+    if (a->action_mode != UAVX_ACTION_CARTESIAN && a->action_mode != UAVX_ACTION_POLAR &&
+        a->action_mode != UAVX_ACTION_POLAR_REFERENCE)
         return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: unknown action_mode");
     if ((reinterpret_cast<uintptr_t>(a->obs) & 15u) || (reinterpret_cast<uintptr_t>(a->actions) & (a->action_dtype == UAVX_F64 ? 15u : 7u)) ||
         (reinterpret_cast<uintptr_t>(a->rew) & 3u) || (reinterpret_cast<uintptr_t>(a->info_distance) & 3u))
@@ -527,7 +477,14 @@ int uavx_uw_step_ex(uavx_uw_handle *h, const uavx_uw_step_args *a, void *stream)
     x.step_cap = a->step_cap; x.seed_lo = (uint32_t)a->seed; x.seed_hi = (uint32_t)(a->seed >> 32);
     x.reset_mask = a->reset_mask; x.ended = a->ended; x.truncated = a->truncated;
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a->action_dtype == UAVX_F64)
+    if (a->action_mode == UAVX_ACTION_POLAR_REFERENCE) {
+        if (a->action_dtype == UAVX_F64)
+            hipLaunchKernelGGL((uw_step_ex_ref_kernel<true>), env_grid(h), dim3(kBlock), 0, st, h->p, x, a->actions,
+                               reinterpret_cast<float4 *>(a->obs), a->rew, a->done, a->info_distance);
+        else
+            hipLaunchKernelGGL((uw_step_ex_ref_kernel<false>), env_grid(h), dim3(kBlock), 0, st, h->p, x, a->actions,
+                               reinterpret_cast<float4 *>(a->obs), a->rew, a->done, a->info_distance);
+    } else if (a->action_dtype == UAVX_F64)
         hipLaunchKernelGGL((uw_step_ex_kernel<true>), env_grid(h), dim3(kBlock), 0, st, h->p, x, a->actions,
                            reinterpret_cast<float4 *>(a->obs), a->rew, a->done, a->info_distance);
     else

@@ -15,6 +15,7 @@ def evaluate_policy(policy_fn, num_agents, episodes=100, max_steps=2000, evaluat
 
     policy_fn(obs [E,N,10] float32 device tensor) -> actions [E,N,2]; with polar=True they are policy
     outputs in [-1,1]^2 converted on the device like test_sac_multi_score.py:47-49, else velocity commands.
+    polar="reference" converts them with the trainers' own dtypes, bit for bit (step_ex).
     An episode ends when all(dones) (:59) or after max_steps (:13,41); its counters are read at that
     moment (:63-64).  Returns dict(success_rate, collision_rate, avg_score, score0, mean_steps)."""
     env = BatchedMultiUAVWorld2D(episodes, num_agents=num_agents, device=device, seed=seed, **env_kwargs)
@@ -58,8 +59,8 @@ def rollout_trajectories(policy_fn, num_agents, episodes=1, max_steps=2000, circ
     :46-47, e.g. with its OFFSET), then step until all(dones) (:75) or max_steps, recording every agent's location
     BEFORE each step (:66) and feeding agents whose `done` flag is set a zero command (:57-59).
 
-    policy_fn(obs [E,N,10]) -> actions [E,N,2] (policy outputs in [-1,1]^2 with polar=True, :61-63; velocity commands
-    otherwise).  Returns dict(positions [T,E,N,2] (float64 when the episode runs in float64-position mode, as the
+    policy_fn(obs [E,N,10]) -> actions [E,N,2] (policy outputs in [-1,1]^2 with polar=True or polar="reference", :61-63;
+    velocity commands otherwise).  Returns dict(positions [T,E,N,2] (float64 when the episode runs in float64-position mode, as the
     reference's does after such pokes), valid [T,E,N] bool (False once the agent is done, or after its world's episode
     is over: the script stops appending), depots [E,N,2], goals [E,N,2], length [E] steps until all(dones) / the cap)."""
     env = BatchedMultiUAVWorld2D(episodes, num_agents=num_agents, device=device, seed=seed, **env_kwargs)

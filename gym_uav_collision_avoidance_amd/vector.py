@@ -21,12 +21,19 @@ per-agent list, MUW:233) and by the batch size:
 """
 import numpy as np
 
+from . import _lib
 from .batched import BatchedMultiUAVWorld2D, BatchedUAVWorld2D
 from .spaces import Box
 
 
 def _batch_box(space, lead):
     return Box.batched(space, lead)
+
+
+
+def _polar(polar):
+    """the `polar` option as step_ex takes it: False, True or "reference" (validated; never bool()-ed into the float32 form)"""
+    return "reference" if _lib.action_mode(polar) == _lib.ACTION_POLAR_REFERENCE else bool(polar)
 
 
 class UAVVectorEnv:
@@ -38,7 +45,7 @@ class UAVVectorEnv:
                  seed=0, env_offset=0, **world_kwargs):
         self.env = BatchedMultiUAVWorld2D(num_envs, device=device, seed=seed, env_offset=env_offset, **world_kwargs)
         self.num_envs, self.num_agents = self.env.num_envs, self.env.num_agents
-        self.auto_reset, self.step_cap, self.polar, self.evaluate = auto_reset, int(step_cap), bool(polar), bool(evaluate)
+        self.auto_reset, self.step_cap, self.polar, self.evaluate = auto_reset, int(step_cap), _polar(polar), bool(evaluate)
         self.device = self.env.device
         self.closed = False
         self._pending = None
@@ -131,7 +138,7 @@ class UAVSingleVectorEnv:
                  **world_kwargs):
         self.env = BatchedUAVWorld2D(num_envs, device=device, seed=seed, env_offset=env_offset, **world_kwargs)
         self.num_envs = self.env.num_envs
-        self.auto_reset, self.step_cap, self.polar = bool(auto_reset), int(step_cap), bool(polar)
+        self.auto_reset, self.step_cap, self.polar = bool(auto_reset), int(step_cap), _polar(polar)
         self.device = self.env.device
         self.closed = False
         self._pending = None

@@ -115,6 +115,10 @@ const char *uavx_build_info(void);
  * correctly rounded square root (csrc/uavx_device.hpp sqrt_rn) against the compiler's IEEE sqrtf on every float32
  * bit pattern.  *mismatches = number of differing results (0 expected).  Synchronous; about 10 ms. */
 int uavx_selftest(int device, uint64_t *mismatches);
+/* The UAVX_ACTION_POLAR_REFERENCE conversion alone, with the device routine the step kernels use: n actions (device memory,
+ * [n*2] float32 or float64 per `action_dtype`) -> n commands out[n*2] (device memory, float64; a float32 action's command
+ * is a float32 value, exact in float64).  `scale` is the float32 speed scale h.  Asynchronous on `stream`. */
+int uavx_polar_commands(const void *actions, int action_dtype, int64_t n, float scale, double *out, void *stream);
 const char *uavx_strerror(int status);
 
 /* ---------------------------------------------------------------------------------------------
@@ -223,8 +227,18 @@ int uavx_step_k(uavx_handle *h, int k, const void *actions, int action_dtype, in
  * (evaluation, :116,161) or a step cap (:17,67).  uavx_step_ex does all three on the device. */
 typedef enum {
     UAVX_ACTION_CARTESIAN = 0, /* actions are velocity commands (what env.step takes) */
-    UAVX_ACTION_POLAR = 1      /* actions are a in [-1,1]^2: v = (a0/2+0.5)*||action_space.high||, theta = a1*pi,
-                                  command = (v cos theta, v sin theta), float32 arithmetic */
+    UAVX_ACTION_POLAR = 1,     /* actions are a in [-1,1]^2: v = (a0/2+0.5)*||action_space.high||, theta = a1*pi,
+                                  command = (v cos theta, v sin theta), float32 arithmetic with a float32 sincospi
+                                  polynomial of a1 (within 4e-6 of the trainers' command; the cheapest launch) */
+    UAVX_ACTION_POLAR_REFERENCE = 2 /* the same conversion as the trainers compute it under NumPy 2 (NEP 50), h the float32
+                                  speed scale (||action_space.high||, UAVWorld2D: action_space.high[0]):
+                                  float32 actions: v = fl32(fl32(a0/2 + 0.5f) * h), theta = fl32(a1 * fl32(pi)),
+                                    c = fl32(cos((double)theta)), s = fl32(sin((double)theta)),
+                                    command = (fl32(v*c), fl32(v*s)), a float32 command;
+                                  float64 actions: v = (a0/2 + 0.5) * (double)h, theta = a1 * pi,
+                                    command = (v cos theta, v sin theta) in double, a float64 command.
+                                  A NaN or infinite a1 gives a NaN command (the reference raises ValueError for +-inf);
+                                  the non-finite counter records it. */
 } uavx_action_mode;
 typedef enum {
     UAVX_RESET_NEVER = 0,       /* like the reference: the caller resets */

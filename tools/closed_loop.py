@@ -115,7 +115,11 @@ if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "gpurun_out", "closed_loop.json"))
     ap.add_argument("--envs", type=int, default=65536)
+    ap.add_argument("--polar", choices=("float32", "reference"), default="float32",
+                    help="step_ex conversion of the actions: polar=True (float32, the default) or polar=\"reference\" (the trainers' "
+                         "expression with their dtypes, bit for bit)")
     args = ap.parse_args()
+    STEP_KW["polar"] = True if args.polar == "float32" else "reference"
     rows = []
     for actor in (GaussianPolicy, TD3Actor, DDPGActor):
         rows.append(workload("BASELINE configs[2]: 65 536 envs x 4 UAVs", args.envs, 4, 0, False, actor))
@@ -136,7 +140,7 @@ if __name__ == "__main__":
     doc = dict(what="closed rollout loop (batched actor forward -> replay action slot -> fused uavx_step_ex into the replay ring) captured "
                     "as one hipGraph per ring pass; random-initialised actors of the reference's architectures (no checkpoint ships with "
                     "the reference); the reference prints the same quantity for its host loop as 'Steps Per Sec' (test_sac_multi.py:120-123)",
-               device=torch.cuda.get_device_name(0), csrc_sha=_lib.source_hash(), actor_sha=_actor_lib.source_hash(), torch=torch.__version__, rows=rows)
+               polar=STEP_KW["polar"], device=torch.cuda.get_device_name(0), csrc_sha=_lib.source_hash(), actor_sha=_actor_lib.source_hash(), torch=torch.__version__, rows=rows)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     json.dump(doc, open(args.out, "w"), indent=1)
     print("wrote", args.out)
