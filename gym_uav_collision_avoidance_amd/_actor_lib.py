@@ -1,6 +1,7 @@
-"""ctypes binding of libuavx_actor.so (include/uavx_actor.h), the fused actor-inference kernels.  Built, checked for
-staleness and loaded like libuavx.so (_lib.py), from a directory of its own so that the environment library and the
-source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device raises."""
+"""ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h), the fused actor-inference, critic
+and TD-target kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
+missing library or device raises."""
 import ctypes
 import os
 import subprocess
@@ -10,6 +11,7 @@ from . import _lib
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "actor_csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_actor.h")
+CRITIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -21,18 +23,24 @@ OK, ERR_INVALID_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_PACKED = 0, -1, -2, -3, -
 # every symbol include/uavx_actor.h declares (tests check the built library exports each of them)
 SYMBOLS = ("uavx_actor_version", "uavx_actor_strerror", "uavx_actor_create", "uavx_actor_destroy", "uavx_actor_pack",
            "uavx_actor_forward")
+# every symbol include/uavx_critic.h declares
+CRITIC_SYMBOLS = ("uavx_critic_version", "uavx_critic_strerror", "uavx_critic_create", "uavx_critic_destroy",
+                  "uavx_critic_set_split_rows", "uavx_critic_pack", "uavx_critic_q", "uavx_critic_target")
+CRITIC_ABI_VERSION = 1
+SPLIT_ROWS = 16384      # UAVX_CRITIC_SPLIT_ROWS: batches below it run the small-batch variant
 
 _lib_handle = None
 
 
 def _sources():
     import glob
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))) + [HEADER]
+    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))) + [HEADER, CRITIC_HEADER]
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped, _lib._code_only) of actor_csrc/*.hip, *.hpp and
-    include/uavx_actor.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override; 16 hex digits."""
+    """sha256 over the code (comments and whitespace dropped, _lib._code_only) of actor_csrc/*.hip, *.hpp,
+    include/uavx_actor.h and include/uavx_critic.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS
+    override; 16 hex digits."""
     import hashlib
     h = hashlib.sha256()
     for f in _sources():
@@ -100,6 +108,18 @@ def load():
     L.uavx_actor_destroy.argtypes = [vp]
     L.uavx_actor_pack.argtypes = [vp] + [vp] * 8 + [vp]
     L.uavx_actor_forward.argtypes = [vp, vp, i64, i64, vp, f32, i32, vp, i64, vp]
+    L.uavx_critic_version.restype = i32
+    if L.uavx_critic_version() != CRITIC_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks critic ABI version {L.uavx_critic_version()}, this package binds "
+                           f"{CRITIC_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_critic_strerror.restype = ctypes.c_char_p
+    L.uavx_critic_strerror.argtypes = [i32]
+    L.uavx_critic_create.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
+    L.uavx_critic_destroy.argtypes = [vp]
+    L.uavx_critic_set_split_rows.argtypes = [vp, i64]
+    L.uavx_critic_pack.argtypes = [vp] + [vp] * 12 + [vp]
+    L.uavx_critic_q.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp]
+    L.uavx_critic_target.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, f32, f32, f32, vp, i64, vp, i64, vp]
     _lib_handle = L
     return L
 
@@ -107,3 +127,8 @@ def load():
 def check(rc, what):
     if rc != OK:
         raise RuntimeError(f"uavx: {what} failed: {load().uavx_actor_strerror(rc).decode()} ({rc})")
+
+
+def check_critic(rc, what):
+    if rc != OK:
+        raise RuntimeError(f"uavx: {what} failed: {load().uavx_critic_strerror(rc).decode()} ({rc})")

@@ -14,53 +14,9 @@
 #include <stdint.h>
 #include <stdlib.h>
 #include "../../include/uavx_actor.h"
+#include "uavx_actor_impl.hpp"
 
 namespace uavx_actor_k {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-constexpr int OBS = 10, ACT = 2, WG = 256, WAVES = WG / 64;
-
-// packed layout of the weights of one actor (element counts; fragments are 64 lanes x EPL elements, lane-major)
-struct Layout {
-    int prec, nb1, nb2, ks1, ks2, ks3, epl;
-    int64_t b1, b2, b3;           // float offsets of the biases (zero padded to whole blocks)
-    int64_t w1, w2, w3;           // element offsets of the fragments, in units of the precision's element
-    int64_t bias_floats, frag_elems;
-};
-
-__host__ __device__ inline Layout layout(int prec, int h1, int h2) {
-    Layout L;
-    L.prec = prec;
-    L.epl = prec == UAVX_ACTOR_F32 ? 1 : 8;
-    L.nb1 = (h1 + 15) / 16;
-    L.nb2 = (h2 + 15) / 16;
-    if (prec == UAVX_ACTOR_BF16) {           // a bf16 step consumes two 16-unit blocks of the previous layer
-        L.nb1 += L.nb1 & 1;
-        L.nb2 += L.nb2 & 1;
-    }
-    L.ks1 = prec == UAVX_ACTOR_F32 ? 3 : 1;                       // K 10 -> 12 (f32) / 32 (bf16)
-    L.ks2 = prec == UAVX_ACTOR_F32 ? 4 * L.nb1 : L.nb1 / 2;
-    L.ks3 = prec == UAVX_ACTOR_F32 ? 4 * L.nb2 : L.nb2 / 2;
-    L.b1 = 0;
-    L.b2 = 16 * L.nb1;
-    L.b3 = L.b2 + 16 * L.nb2;
-    L.bias_floats = L.b3 + 16;
-    L.w1 = 0;
-    L.w2 = L.w1 + (int64_t)L.nb1 * L.ks1 * 64 * L.epl;
-    L.w3 = L.w2 + (int64_t)L.nb2 * L.ks2 * 64 * L.epl;
-    L.frag_elems = L.w3 + (int64_t)L.ks3 * 64 * L.epl;
-    return L;
-}
-
-// row k of the input that element e of lane `lane` in MFMA step ks multiplies (see the header comment)
-__device__ inline int k_of(int prec, bool first, int ks, int lane, int e) {
-    const int g = lane >> 4;
-    if (prec == UAVX_ACTOR_F32)
-        return first ? 4 * ks + g : 16 * (ks >> 2) + 4 * g + (ks & 3);
-    return first ? 8 * g + e : 16 * (2 * ks + (e >> 2)) + 4 * g + (e & 3);
-}
 
 struct PackArgs {
     const float *W1, *b1, *W2, *b2, *W3, *b3, *W3b, *b3b;
@@ -96,15 +52,6 @@ __global__ __launch_bounds__(256) void pack_kernel(PackArgs a, Layout L, float *
     else if (k < a.h2) v = n < 2 ? a.W3[(int64_t)n * a.h2 + k] : n < a.nout ? a.W3b[(int64_t)(n - 2) * a.h2 + k] : 0.f;
     if (L.prec == UAVX_ACTOR_F32) ((float *)frags)[f] = v;
     else ((__bf16 *)frags)[f] = (__bf16)v;        // round to nearest even (v_cvt_pk_bf16_f32)
-}
-
-template <bool LEAKY>
-__device__ inline float act(float x) {
-    return LEAKY ? (x > 0.f ? x : 0.01f * x) : (x > 0.f ? x : (x != x ? x : 0.f));   // NaN passes like torch's relu
-}
-
-__device__ inline float clampf(float x, float lo, float hi) {   // torch.clamp: NaN stays NaN
-    return x < lo ? lo : (x > hi ? hi : x);
 }
 
 struct FwdArgs {
@@ -263,14 +210,6 @@ __global__ __launch_bounds__(WG, WPS) void actor_fwd(FwdArgs a, const float *__r
 }  // namespace uavx_actor_k
 
 using namespace uavx_actor_k;
-
-struct uavx_actor {
-    int kind, prec, h1, h2;
-    Layout L;
-    float *bias;        // device: L.bias_floats floats, then the fragments
-    void *frags;
-    bool packed;
-};
 
 namespace {
 

@@ -1,0 +1,242 @@
+"""FusedCritic and FusedTarget: the no-grad forward blocks of the reference's learners as ONE HIP launch each
+(libuavx_actor.so, include/uavx_critic.h) instead of a chain of torch layers and element-wise kernels.
+
+    critic = FusedCritic.from_module(critic_target)                # TwinQ, TD3TwinQ or DDPGCritic
+    q1, q2 = critic.q(state, action)                               # what the module's forward returns
+    target = FusedTarget(actor_target, critic_target)              # the learner is told from the pair
+    s, a, r, s2, m = mem.sample(256)
+    y = target(s2, r, m, generator=g)                              # TD3's target_Q; SAC also takes alpha=
+
+FusedTarget computes, in one launch, the block that opens each learner's update (the next action never leaves the chip):
+    SAC   a', logπ = policy.sample(s')      y = r + mask·γ·(min(Q1', Q2')(s', a') − α·logπ)      (sac.py:56-60)
+    TD3   a' = clamp(actor(s') + clamp(policy_noise·ε, ±noise_clip), ±1)   y = r + not_done·γ·min(Q1', Q2')(s', a')
+    DDPG  a' = actor(s')                    y = r + γ·mask·Q'(s', a')                              (ddpg.py:62)
+The packed weights are a SNAPSHOT taken at construction / refresh(): after an optimiser step or soft update the fused
+networks keep computing with the old weights until refresh() is called.  Inputs must be float32 on the handle's device;
+anything else raises (no conversion, no CPU path)."""
+import ctypes
+
+import torch
+
+from . import _actor_lib
+from .fused_actor import FusedActor
+from .policy import DDPGCritic, TD3TwinQ, TwinQ
+
+_PRECISIONS = {"f32": _actor_lib.F32, "bf16": _actor_lib.BF16}
+_KIND_NAMES = {_actor_lib.SAC: "SAC", _actor_lib.TD3: "TD3", _actor_lib.DDPG: "DDPG"}
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _check_f32(t, device, what):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != device:
+        raise TypeError(f"uavx: {what} must be a float32 tensor on {device}, got {getattr(t, 'dtype', type(t))} on "
+                        f"{getattr(t, 'device', 'host')}")
+
+
+def _rows2(t, cols, device, what):
+    """t [B, cols] float32 on device with unit last stride -> (B, row stride)."""
+    _check_f32(t, device, what)
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError(f"uavx: {what} must be [B, {cols}], got {tuple(t.shape)}")
+    if t.shape[0] and t.stride(1) != 1:
+        raise ValueError(f"uavx: {what} must have unit stride along its last dimension")
+    return t.shape[0], (t.stride(0) if t.shape[0] > 1 else cols)
+
+
+def _column(t, rows, device, what):
+    """t [B] or [B, 1] float32 on device, any row stride -> row stride."""
+    _check_f32(t, device, what)
+    if tuple(t.shape) not in ((rows,), (rows, 1)):
+        raise ValueError(f"uavx: {what} must be [{rows}] or [{rows}, 1], got {tuple(t.shape)}")
+    return t.stride(0) if rows > 1 else 1
+
+
+class FusedCritic:
+    def __init__(self, module, precision="f32"):
+        if isinstance(module, TwinQ):
+            kind = _actor_lib.SAC
+            layers = (module.linear1, module.linear2, module.linear3, module.linear4, module.linear5, module.linear6)
+        elif isinstance(module, TD3TwinQ):
+            kind, layers = _actor_lib.TD3, (module.l1, module.l2, module.l3, module.l4, module.l5, module.l6)
+        elif isinstance(module, DDPGCritic):
+            kind, layers = _actor_lib.DDPG, (module.input, module.fc1, module.fc2)
+        else:
+            raise TypeError(f"uavx: FusedCritic takes a TwinQ, TD3TwinQ or DDPGCritic, not {type(module).__name__}")
+        if precision not in _PRECISIONS:
+            raise ValueError(f"uavx: precision must be one of {sorted(_PRECISIONS)}, not {precision!r}")
+        w = layers[0].weight
+        if w.device.type != "cuda":
+            raise ValueError(f"uavx: FusedCritic needs the module on a GPU (cuda:N), its parameters are on {w.device}")
+        for lin in layers:
+            if lin.weight.dtype != torch.float32 or lin.bias is None or lin.bias.dtype != torch.float32:
+                raise TypeError("uavx: FusedCritic packs float32 parameters; keep the module in float32 and pick "
+                                "precision='bf16' for the bf16 kernel")
+        self.act_dim = 2
+        self.obs_dim = layers[0].in_features - self.act_dim
+        self.hidden1, self.hidden2 = layers[0].out_features, layers[1].out_features
+        if len(layers) == 6 and tuple(l.weight.shape for l in layers[:3]) != tuple(l.weight.shape for l in layers[3:]):
+            raise ValueError("uavx: the two towers of a twin critic must have the same shapes")
+        self.module, self.kind, self.precision, self.device = module, kind, precision, w.device
+        self.towers = 2 if len(layers) == 6 else 1
+        self._layers = layers
+        self._lib = _actor_lib.load()
+        h = ctypes.c_void_p()
+        with torch.cuda.device(self.device):
+            rc = self._lib.uavx_critic_create(kind, _PRECISIONS[precision], self.obs_dim, self.hidden1, self.hidden2,
+                                              self.act_dim, ctypes.byref(h))
+        _actor_lib.check_critic(rc, f"uavx_critic_create({type(module).__name__}, {layers[0].in_features}->{self.hidden1}->"
+                                    f"{self.hidden2}->1, {precision})")
+        self._h = h
+        self.refresh()
+
+    @classmethod
+    def from_module(cls, module, precision="f32"):
+        """module: a TwinQ, TD3TwinQ or DDPGCritic (e.g. what policy.load_critic returns), float32, on a GPU."""
+        return cls(module, precision)
+
+    def refresh(self):
+        """Re-packs the module's current parameters (one launch on the current stream)."""
+        ps = []
+        for lin in self._layers:
+            ps += [lin.weight.detach().contiguous(), lin.bias.detach().contiguous()]
+        self._keep = ps
+        ptrs = [p.data_ptr() for p in ps] + [None] * (12 - len(ps))
+        _actor_lib.check_critic(self._lib.uavx_critic_pack(self._h, *ptrs, _stream(self.device)), "uavx_critic_pack")
+        return self
+
+    def set_split_rows(self, rows):
+        """Batches below `rows` run the small-batch variant (default _actor_lib.SPLIT_ROWS; 0 = never)."""
+        _actor_lib.check_critic(self._lib.uavx_critic_set_split_rows(self._h, int(rows)), "uavx_critic_set_split_rows")
+        return self
+
+    @torch.no_grad()
+    def q(self, state, action, out=None):
+        """(q1, q2), each [B, 1], for a twin critic, q [B, 1] for DDPG: the module's forward on [B, 10] states and [B, 2]
+        actions.  out: an optional float32 [B, 2] (twin) / [B, 1] tensor written in place; the results are views of it."""
+        rows, s_stride = _rows2(state, self.obs_dim, self.device, "state")
+        arows, a_stride = _rows2(action, self.act_dim, self.device, "action")
+        if arows != rows:
+            raise ValueError(f"uavx: state and action rows differ ({rows} vs {arows})")
+        cols = self.towers
+        if out is None:
+            out = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
+        else:
+            _rows2(out, cols, self.device, "out")
+            if out.shape[0] != rows:
+                raise ValueError(f"uavx: out must be [{rows}, {cols}], got {tuple(out.shape)}")
+        o_stride = out.stride(0) if rows > 1 else cols
+        rc = self._lib.uavx_critic_q(self._h, state.data_ptr(), rows, s_stride, action.data_ptr(), a_stride, out.data_ptr(),
+                                     o_stride, _stream(self.device))
+        _actor_lib.check_critic(rc, "uavx_critic_q")
+        return (out[:, 0:1], out[:, 1:2]) if cols == 2 else out
+
+    __call__ = q
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.uavx_critic_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class FusedTarget:
+    """The learner's TD target from a (next-action actor, target critic) pair: SAC (GaussianPolicy, TwinQ), TD3
+    (TD3Actor, TD3TwinQ) or DDPG (DDPGActor, DDPGCritic).  actor / critic: modules or FusedActor / FusedCritic of the
+    same precision.  gamma, policy_noise, noise_clip: the learners' defaults (sac.py gamma, td3.py:71-74)."""
+
+    def __init__(self, actor, critic, precision="f32", gamma=0.99, policy_noise=0.2, noise_clip=0.5):
+        self._owned = []
+        if not isinstance(actor, FusedActor):
+            actor = FusedActor.from_module(actor, precision)
+            self._owned.append(actor)
+        if not isinstance(critic, FusedCritic):
+            critic = FusedCritic.from_module(critic, precision)
+            self._owned.append(critic)
+        if actor.kind != critic.kind:
+            raise TypeError(f"uavx: FusedTarget pairs a {_KIND_NAMES[actor.kind]} actor ({type(actor.module).__name__}) "
+                            f"with a {_KIND_NAMES[critic.kind]} critic ({type(critic.module).__name__})")
+        if actor.precision != critic.precision:
+            raise ValueError(f"uavx: actor ({actor.precision}) and critic ({critic.precision}) precisions differ")
+        if actor.device != critic.device:
+            raise ValueError(f"uavx: actor ({actor.device}) and critic ({critic.device}) are on different devices")
+        self.actor, self.critic, self.kind = actor, critic, critic.kind
+        self.precision, self.device = critic.precision, critic.device
+        self.gamma, self.policy_noise, self.noise_clip = float(gamma), float(policy_noise), float(noise_clip)
+        self._alpha = torch.zeros(1, dtype=torch.float32, device=self.device)   # holds a float alpha on the device
+
+    @property
+    def learner(self):
+        return _KIND_NAMES[self.kind].lower()
+
+    def refresh(self):
+        """Re-packs both networks (two launches on the current stream; capturable)."""
+        self.actor.refresh()
+        self.critic.refresh()
+        return self
+
+    def set_split_rows(self, rows):
+        self.critic.set_split_rows(rows)
+        return self
+
+    @torch.no_grad()
+    def __call__(self, next_state, reward, mask, alpha=None, generator=None, noise=None, out=None, aux=None):
+        """y [B, 1] float32 (next_q_value / target_Q / y).  next_state [B, 10] (any row stride, e.g. a view of the replay
+        ring); reward, mask [B] or [B, 1] with any row stride; alpha (SAC): a float or a 1-element float32 device tensor,
+        read when the kernel runs; eps ~ torch.randn((B, 2), generator=generator) drawn as FusedActor.act draws it, or
+        `noise` ([B, 2] float32) given; out: optional [B, 1] / [B] float32 written in place; aux: optional [B, 4] float32
+        receiving a'0, a'1, logπ (0 unless SAC), min Q."""
+        dev = self.device
+        rows, s_stride = _rows2(next_state, self.critic.obs_dim, dev, "next_state")
+        r_stride = _column(reward, rows, dev, "reward")
+        m_stride = _column(mask, rows, dev, "mask")
+        if out is None:
+            out = torch.empty((rows, 1), dtype=torch.float32, device=dev)
+        o_stride = _column(out, rows, dev, "out")
+        a_ptr, a_stride = None, 4
+        if aux is not None:
+            arows, a_stride = _rows2(aux, 4, dev, "aux")
+            if arows != rows:
+                raise ValueError(f"uavx: aux must be [{rows}, 4], got {tuple(aux.shape)}")
+            a_ptr = aux.data_ptr()
+        eps_ptr = None
+        if self.kind != _actor_lib.DDPG:
+            if noise is None:
+                noise = torch.randn((rows, 2), generator=generator, device=dev, dtype=torch.float32)
+            else:
+                nrows, _ = _rows2(noise, 2, dev, "noise")
+                if nrows != rows or (rows > 1 and noise.stride(0) != 2):
+                    raise ValueError(f"uavx: noise must be a contiguous [{rows}, 2] tensor")
+            eps_ptr = noise.data_ptr()
+        alpha_ptr = None
+        if self.kind == _actor_lib.SAC:
+            if alpha is None:
+                raise ValueError("uavx: a SAC target needs alpha (a float or a 1-element float32 device tensor)")
+            if torch.is_tensor(alpha):
+                _check_f32(alpha, dev, "alpha")
+                if alpha.numel() != 1:
+                    raise ValueError(f"uavx: alpha must have one element, got {tuple(alpha.shape)}")
+                alpha_ptr = alpha.data_ptr()
+            else:
+                self._alpha.fill_(float(alpha))
+                alpha_ptr = self._alpha.data_ptr()
+        self._keep = noise
+        rc = self.critic._lib.uavx_critic_target(
+            self.critic._h, self.actor._h, next_state.data_ptr(), rows, s_stride, reward.data_ptr(), r_stride,
+            mask.data_ptr(), m_stride, eps_ptr, alpha_ptr, self.gamma, self.policy_noise, self.noise_clip, out.data_ptr(),
+            o_stride, a_ptr, a_stride, _stream(dev))
+        _actor_lib.check_critic(rc, "uavx_critic_target")
+        return out
+
+    def close(self):
+        """Releases the handles this target built from modules (a FusedActor / FusedCritic passed in stays open)."""
+        for h in self._owned:
+            h.close()
+        self._owned = []

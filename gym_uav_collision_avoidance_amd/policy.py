@@ -267,6 +267,63 @@ def save_ddpg_checkpoint(directory, actor, critic=None, actor_optimizer=None, cr
     return directory
 
 
+def _ckpt_kind(path):
+    import os
+    f = os.path.join(path, "actor.chpt") if os.path.isdir(path) else path
+    keys = set(torch.load(f, map_location="cpu", weights_only=True))
+    return "sac" if "policy_state_dict" in keys else "td3" if "actor_state_dict" in keys else "ddpg" if "model_state_dict" in keys else None
+
+
+def _load_module(cls, sd, device, **dims):
+    m = cls(**dims).to(device)
+    m.load_state_dict(sd)
+    return m.eval()
+
+
+def load_critic(path, kind=None, target=True, device="cuda", num_inputs=10, num_actions=2):
+    """Loads the critic (target=True: the target critic) of a reference checkpoint (tensors only: weights_only=True):
+        SAC   weights.chpt  'critic_target_state_dict' / 'critic_state_dict'  -> TwinQ      (sac.py:101-114)
+        TD3   weights.chpt  'critic_target_state_dict' / 'critic_state_dict'  -> TD3TwinQ   (td3.py:159-170)
+        DDPG  critic.chpt   'target_model_state_dict' / 'model_state_dict'    -> DDPGCritic (ddpg.py:124-135)
+    `path`: the checkpoint file (SAC / TD3), or DDPG's checkpoint directory or its critic.chpt.  kind: "sac" / "td3" /
+    "ddpg", or None to tell from the keys."""
+    import os
+    kind = _ckpt_kind(path) if kind is None else kind
+    if kind in ("sac", "td3"):
+        ckpt = torch.load(path, map_location=device, weights_only=True)
+        sd = ckpt["critic_target_state_dict" if target else "critic_state_dict"]
+        first = "linear1.weight" if kind == "sac" else "l1.weight"
+        return _load_module(TwinQ if kind == "sac" else TD3TwinQ, sd, device, num_inputs=num_inputs,
+                            num_actions=num_actions, hidden=sd[first].shape[0])
+    if kind == "ddpg":
+        f = os.path.join(path, "critic.chpt") if os.path.isdir(path) else path
+        ckpt = torch.load(f, map_location=device, weights_only=True)
+        sd = ckpt["target_model_state_dict" if target else "model_state_dict"]
+        return _load_module(DDPGCritic, sd, device, num_inputs=num_inputs, num_actions=num_actions,
+                            hidden1=sd["input.weight"].shape[0], hidden2=sd["fc1.weight"].shape[0])
+    raise ValueError(f"uavx: {path} is not a SAC / TD3 / DDPG checkpoint of the reference's layouts")
+
+
+def load_target_networks(path, kind=None, device="cuda"):
+    """(actor, critic) of the no-grad target block of the learner that wrote `path`, for fused_critic.FusedTarget:
+    SAC (the LIVE policy, sac.py:57, and critic_target), TD3 (actor_target, critic_target), DDPG (the target_model of
+    actor.chpt and of critic.chpt).  `path`: SAC / TD3 weights.chpt, or DDPG's checkpoint directory."""
+    import os
+    kind = _ckpt_kind(path) if kind is None else kind
+    if kind == "sac":
+        actor = load_reference_checkpoint(path, device=device)
+    elif kind == "td3":
+        sd = torch.load(path, map_location=device, weights_only=True)["actor_target_state_dict"]
+        actor = _load_module(TD3Actor, sd, device, hidden=sd["l1.weight"].shape[0])
+    elif kind == "ddpg":
+        f = os.path.join(path, "actor.chpt") if os.path.isdir(path) else path
+        sd = torch.load(f, map_location=device, weights_only=True)["target_model_state_dict"]
+        actor = _load_module(DDPGActor, sd, device, hidden1=sd["input.weight"].shape[0], hidden2=sd["fc1.weight"].shape[0])
+    else:
+        raise ValueError(f"uavx: {path} is not a SAC / TD3 / DDPG checkpoint of the reference's layouts")
+    return actor, load_critic(path, kind=kind, target=True, device=device)
+
+
 def load_actor(path, kind=None, device="cuda"):
     """Loads whichever of the three reference actors `path` holds (kind: "sac" / "td3" / "ddpg", or None to tell from the keys)."""
     import os

@@ -1,0 +1,151 @@
+"""Host-side checks of the fused critic / TD-target half of libuavx_actor.so (include/uavx_critic.h): it builds for gfx950
+without a GPU, its hash covers the critic header, it exports what the header declares, it rejects bad arguments before
+touching a device, its kernels neither spill nor use scratch, and the actor kernels keep their recorded resources."""
+import ctypes
+import importlib.util
+import json
+import os
+import re
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _alib():
+    from gym_uav_collision_avoidance_amd import _actor_lib
+    _actor_lib.build()
+    return _actor_lib
+
+
+def _kernels():
+    spec = importlib.util.spec_from_file_location("kernel_resources", os.path.join(ROOT, "tools", "kernel_resources.py"))
+    kr = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(kr)
+    return kr.kernel_table(_alib().LIB_PATH)
+
+
+def test_critic_library_cross_compiles_and_hash_covers_header():
+    a = _alib()
+    assert a.CRITIC_HEADER in a._sources()
+    assert any(f.endswith("uavx_critic.hip") for f in a._sources())
+    blob = open(a.LIB_PATH, "rb").read()
+    assert f"UAVX_ACTOR_SRC_HASH={a.source_hash()}".encode() in blob
+    mk = open(os.path.join(a.CSRC, "Makefile")).read()
+    assert "uavx_critic.hip" in mk and "uavx_critic.h" in mk
+
+
+def test_critic_exports_every_declared_symbol():
+    a = _alib()
+    hdr = open(os.path.join(ROOT, "include", "uavx_critic.h")).read()
+    declared = set(re.findall(r"\b(uavx_critic_[a-z_0-9]+)\s*\(", hdr))
+    assert declared == set(a.CRITIC_SYMBOLS), declared ^ set(a.CRITIC_SYMBOLS)
+    assert set(a.SYMBOLS).isdisjoint(a.CRITIC_SYMBOLS)
+    lib = a.load()
+    for name in sorted(declared):
+        assert hasattr(lib, name), name
+    assert lib.uavx_critic_version() == 1
+    assert lib.uavx_critic_strerror(a.ERR_INVALID_ARG) == b"invalid argument"
+    assert lib.uavx_critic_strerror(a.ERR_UNSUPPORTED) == b"no kernel compiled for these dimensions"
+    assert lib.uavx_critic_strerror(a.ERR_NOT_PACKED) == b"q / target before pack"
+    assert f"#define UAVX_CRITIC_SPLIT_ROWS {a.SPLIT_ROWS}" in hdr
+
+
+def test_critic_bad_arguments_rejected_before_any_device_call():
+    a = _alib()
+    lib = a.load()
+    h = ctypes.c_void_p()
+    create = lambda *args: lib.uavx_critic_create(*args, ctypes.byref(h))
+    assert create(3, a.F32, 10, 256, 256, 2) == a.ERR_INVALID_ARG          # unknown kind
+    assert create(-1, a.F32, 10, 256, 256, 2) == a.ERR_INVALID_ARG
+    assert create(a.SAC, 2, 10, 256, 256, 2) == a.ERR_INVALID_ARG          # unknown precision
+    assert create(a.TD3, a.F32, 10, 0, 256, 2) == a.ERR_INVALID_ARG        # empty layer
+    assert create(a.TD3, a.F32, 10, 256, -4, 2) == a.ERR_INVALID_ARG
+    assert create(a.TD3, a.F32, 11, 256, 256, 2) == a.ERR_UNSUPPORTED      # not the env's observation
+    assert create(a.TD3, a.F32, 10, 256, 256, 3) == a.ERR_UNSUPPORTED
+    assert create(a.SAC, a.F32, 10, 128, 256, 2) == a.ERR_UNSUPPORTED      # no register tile for 128 units
+    assert create(a.DDPG, a.BF16, 10, 256, 300, 2) == a.ERR_UNSUPPORTED    # 256 is not a DDPG tile
+    assert create(a.SAC, a.F32, 10, 256, 4097, 2) == a.ERR_UNSUPPORTED
+    assert h.value is None                                                 # a failed create leaves the handle NULL
+    assert lib.uavx_critic_create(a.TD3, a.F32, 10, 256, 256, 2, None) == a.ERR_INVALID_ARG
+    buf = ctypes.c_void_p(16)     # never dereferenced: every call below fails its argument check first
+    nul = None
+    # NULL handles (the checks that need a live handle run in tests/test_gpu_critic.py)
+    assert lib.uavx_critic_q(nul, buf, 4, 10, buf, 2, buf, 2, nul) == a.ERR_INVALID_ARG
+    assert lib.uavx_critic_pack(nul, *([buf] * 6), *([nul] * 6), nul) == a.ERR_INVALID_ARG
+    assert lib.uavx_critic_destroy(nul) == a.ERR_INVALID_ARG
+    assert lib.uavx_critic_set_split_rows(nul, 10) == a.ERR_INVALID_ARG
+    # target: NULL handles
+    assert lib.uavx_critic_target(nul, nul, buf, 4, 10, buf, 1, buf, 1, buf, buf, 0.99, 0.2, 0.5, buf, 1, nul, 4,
+                                  nul) == a.ERR_INVALID_ARG
+
+
+def test_critic_kernels_no_spills_no_scratch():
+    rows = _kernels()
+    names = sorted(r["name"] for r in rows)
+    fwd = [n for n in names if n.startswith("uavx_critic_k::critic_fwd<")]
+    # 4 register tiles (f32 / bf16 x twin / DDPG) x {q, target} x {large-batch, small-batch}
+    assert len(fwd) == 16, fwd
+    assert sum(n.startswith("uavx_critic_k::critic_pack_kernel") for n in names) == 1, names
+    for r in rows:
+        assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0, r
+        assert r["private_segment_fixed_size"] == 0, r
+    for r in rows:
+        m = re.match(r"uavx_critic_k::critic_fwd<(\d+), (\w+), (\d+), (\d+), (\d+), (\d+), (\w+)>", r["name"])
+        if m:
+            s, wps = int(m.group(5)), int(m.group(6))
+            assert r["waves_per_simd"] >= wps, r
+            assert r["max_flat_workgroup_size"] == (256 if s == 1 else 64 * s), r
+            if s > 1:
+                assert int(m.group(4)) == 1, r                       # one row block per workgroup
+                assert r["group_segment_fixed_size"] == 2 * s * 64 * 16, r
+
+
+def test_actor_kernels_keep_their_recorded_resources():
+    """The critic shares a header with uavx_actor.hip: the actor's four forward tiles and its pack kernel keep the symbols
+    and register counts recorded when they were measured (profiles/r05_actor_kernel_resources.json)."""
+    rec = json.load(open(os.path.join(ROOT, "profiles", "r05_actor_kernel_resources.json")))
+    now = {r["symbol"]: r for r in _kernels() if r["name"].startswith("uavx_actor_k::")}
+    assert set(now) == {r["symbol"] for r in rec}
+    for r in rec:
+        for f in ("vgpr_count", "agpr_count", "sgpr_count", "group_segment_fixed_size", "kernarg_segment_size"):
+            assert now[r["symbol"]][f] == r[f], (r["name"], f, now[r["symbol"]][f], r[f])
+
+
+def test_python_critic_api_rejects_bad_modules_before_the_device():
+    import pytest
+    import torch
+    from gym_uav_collision_avoidance_amd import policy
+    from gym_uav_collision_avoidance_amd.fused_critic import FusedCritic, FusedTarget
+    with pytest.raises(TypeError):
+        FusedCritic.from_module(policy.TD3Actor())                  # not a critic
+    with pytest.raises(ValueError):
+        FusedCritic.from_module(policy.TwinQ(), precision="f16")
+    with pytest.raises(ValueError):
+        FusedCritic.from_module(policy.TwinQ())                     # CPU parameters: no CPU path
+    with pytest.raises(ValueError):
+        FusedTarget(policy.TD3Actor(), policy.TD3TwinQ())          # CPU actor
+    assert torch.float32 == policy.TwinQ().linear1.weight.dtype
+
+
+def test_critic_loaders_read_the_reference_layouts(tmp_path):
+    import torch
+    from gym_uav_collision_avoidance_amd import policy
+    torch.manual_seed(0)
+    sac, tw = policy.GaussianPolicy(), policy.TwinQ()
+    tgt = policy.TwinQ()
+    p = policy.save_reference_checkpoint(str(tmp_path / "sac.chpt"), sac, critic=tw, critic_target=tgt)
+    c = policy.load_critic(p, device="cpu")
+    assert isinstance(c, policy.TwinQ) and torch.equal(c.linear5.weight, tgt.linear5.weight)
+    assert torch.equal(policy.load_critic(p, target=False, device="cpu").linear5.weight, tw.linear5.weight)
+    a, c = policy.load_target_networks(p, device="cpu")
+    assert isinstance(a, policy.GaussianPolicy) and torch.equal(a.linear2.weight, sac.linear2.weight)
+    td3, tq = policy.TD3Actor(), policy.TD3TwinQ()
+    p = policy.save_td3_checkpoint(str(tmp_path / "td3.chpt"), td3, critic=tq)
+    a, c = policy.load_target_networks(p, device="cpu")
+    assert isinstance(a, policy.TD3Actor) and isinstance(c, policy.TD3TwinQ)
+    assert torch.equal(a.l3.weight, td3.l3.weight) and torch.equal(c.l6.weight, tq.l6.weight)
+    dd, dc = policy.DDPGActor(), policy.DDPGCritic()
+    d = policy.save_ddpg_checkpoint(str(tmp_path / "ddpg"), dd, critic=dc)
+    a, c = policy.load_target_networks(d, device="cpu")
+    assert isinstance(a, policy.DDPGActor) and isinstance(c, policy.DDPGCritic)
+    assert torch.equal(c.fc1.weight, dc.fc1.weight) and torch.equal(a.fc1.weight, dd.fc1.weight)
+    assert torch.equal(policy.load_critic(os.path.join(d, "critic.chpt"), kind="ddpg", device="cpu").fc2.weight, dc.fc2.weight)
