@@ -259,7 +259,8 @@ int uavx_actor_create(int kind, int precision, int obs_dim, int hidden1, int hid
         return UAVX_ACTOR_ERR_INVALID_ARG;
     if (obs_dim != OBS || act_dim != ACT || hidden2 > 4096) return UAVX_ACTOR_ERR_UNSUPPORTED;
     const Layout L = layout(precision, hidden1, hidden2);
-    if (!find(precision, kind == UAVX_ACTOR_DDPG, L.nb1)) return UAVX_ACTOR_ERR_UNSUPPORTED;
+    if (!hidden_supported(kind, hidden1, hidden2) || !find(precision, kind == UAVX_ACTOR_DDPG, L.nb1))
+        return UAVX_ACTOR_ERR_UNSUPPORTED;
     const size_t esz = precision == UAVX_ACTOR_F32 ? 4 : 2;
     void *mem = nullptr;
     if (hipMalloc(&mem, L.bias_floats * 4 + L.frag_elems * esz) != hipSuccess) {

@@ -45,6 +45,15 @@ __host__ __device__ inline Layout layout(int prec, int h1, int h2) {
     return L;
 }
 
+// The hidden sizes uavx_actor_create and uavx_critic_create accept, for both precisions (include/uavx_actor.h,
+// include/uavx_critic.h): hidden1 within the last 16-unit block of a compiled register tile (SAC / TD3 241..256, DDPG
+// 385..400), hidden2 1..4096.  bf16 rounds nb1 up to an even block count, so a lookup by nb1 alone would also accept
+// 225..240 and 401..416 there.
+inline bool hidden_supported(int kind, int h1, int h2) {
+    const int top = kind == UAVX_ACTOR_DDPG ? 400 : 256;
+    return h1 > top - 16 && h1 <= top && h2 >= 1 && h2 <= 4096;
+}
+
 // row k of the input that element e of lane `lane` in MFMA step ks multiplies (see the header comment)
 __device__ inline int k_of(int prec, bool first, int ks, int lane, int e) {
     const int g = lane >> 4;

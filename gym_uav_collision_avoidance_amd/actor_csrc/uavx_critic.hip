@@ -406,7 +406,8 @@ int uavx_critic_create(int kind, int precision, int obs_dim, int hidden1, int hi
         return UAVX_CRITIC_ERR_INVALID_ARG;
     if (obs_dim != OBS || act_dim != 2 || hidden2 > 4096) return UAVX_CRITIC_ERR_UNSUPPORTED;
     const Layout L = uavx_actor_k::layout(precision, hidden1, hidden2);
-    if (!find(precision, kind == UAVX_CRITIC_DDPG, L.nb1)) return UAVX_CRITIC_ERR_UNSUPPORTED;
+    if (!uavx_actor_k::hidden_supported(kind, hidden1, hidden2) || !find(precision, kind == UAVX_CRITIC_DDPG, L.nb1))
+        return UAVX_CRITIC_ERR_UNSUPPORTED;
     const int towers = kind == UAVX_CRITIC_DDPG ? 1 : 2;
     const size_t esz = precision == UAVX_CRITIC_F32 ? 4 : 2;
     void *mem = nullptr;

@@ -53,8 +53,8 @@ int uavx_actor_version(void);
 const char *uavx_actor_strerror(int status);
 
 /* obs_dim 10 and act_dim 2 (the environment's); hidden1 in 241..256 for SAC / TD3 and 385..400 for DDPG (the reference's
- * 256 and 400, whose register tiles this build compiles), hidden2 in 1..4096.  Allocates the packed weight buffer on the
- * current device. */
+ * 256 and 400, whose register tiles this build compiles), hidden2 in 1..4096, for both precisions.  Allocates the packed
+ * weight buffer on the current device. */
 int uavx_actor_create(int kind, int precision, int obs_dim, int hidden1, int hidden2, int act_dim, uavx_actor **out);
 int uavx_actor_destroy(uavx_actor *h);
 

@@ -55,7 +55,8 @@ int uavx_critic_version(void);
 const char *uavx_critic_strerror(int status);
 
 /* obs_dim 10 and act_dim 2; hidden1 in 241..256 for SAC / TD3 and 385..400 for DDPG (the actor's compiled register tiles),
- * hidden2 in 1..4096.  Allocates the packed weight buffer on the current device.  *out stays NULL on failure. */
+ * hidden2 in 1..4096, for both precisions.  Allocates the packed weight buffer on the current device.  *out stays NULL on
+ * failure. */
 int uavx_critic_create(int kind, int precision, int obs_dim, int hidden1, int hidden2, int act_dim, uavx_critic **out);
 int uavx_critic_destroy(uavx_critic *h);
 

@@ -84,3 +84,12 @@ def test_actor_kernels_no_spills_no_scratch():
         m = re.match(r"uavx_actor_k::actor_fwd<\d+, \w+, \d+, \d+, (\d+)>", r["name"])
         if m:
             assert r["waves_per_simd"] >= int(m.group(1)), r
+
+
+
+def test_actor_create_accepts_exactly_the_documented_hidden_sizes():
+    """hidden1 241..256 (SAC / TD3) or 385..400 (DDPG) and hidden2 1..4096, for both precisions (tests/fused_ref.py)."""
+    from fused_ref import check_hidden_range
+    a = _alib()
+    lib = a.load()
+    check_hidden_range(lib.uavx_actor_create, lib.uavx_actor_destroy, a.OK, a.ERR_INVALID_ARG, a.ERR_UNSUPPORTED, a.ERR_HIP)

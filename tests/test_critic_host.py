@@ -149,3 +149,12 @@ def test_critic_loaders_read_the_reference_layouts(tmp_path):
     assert isinstance(a, policy.DDPGActor) and isinstance(c, policy.DDPGCritic)
     assert torch.equal(c.fc1.weight, dc.fc1.weight) and torch.equal(a.fc1.weight, dd.fc1.weight)
     assert torch.equal(policy.load_critic(os.path.join(d, "critic.chpt"), kind="ddpg", device="cpu").fc2.weight, dc.fc2.weight)
+
+
+def test_critic_create_accepts_exactly_the_documented_hidden_sizes():
+    """The actor's range, for both precisions: hidden1 241..256 (SAC / TD3) or 385..400 (DDPG), hidden2 1..4096."""
+    from fused_ref import check_hidden_range
+    a = _alib()
+    lib = a.load()
+    check_hidden_range(lib.uavx_critic_create, lib.uavx_critic_destroy, a.OK, a.ERR_INVALID_ARG, a.ERR_UNSUPPORTED,
+                       a.ERR_HIP)
