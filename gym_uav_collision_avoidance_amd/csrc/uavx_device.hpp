@@ -115,28 +115,34 @@ __device__ __forceinline__ float wrap_pi(float x) {
     return fmaf(-k, kTwoPi, x);
 }
 
-// atan2f for finite inputs, ~2 ulp: octant reduction + Cephes atanf polynomial on |t| <= tan(pi/8).
+// wrap_pi(x) / pi for x in [-2pi, 2pi]: 2 fract(x / 2pi + 1/2) - 1, in [-1, 1) -- three instructions for the four of
+// wrap_pi and the scaling (observation features, compared on the circle; |error| < 2.4e-7).
+__device__ __forceinline__ float wrap_unit(float x) {
+    return fmaf(__builtin_amdgcn_fractf(fmaf(x, kInvTwoPi, 0.5f)), 2.0f, -1.0f);
+}
+
+// atan2f for finite inputs, |error| < 7e-7 rad: t = min(|x|,|y|) / max(|x|,|y|) in [0, 1] and one odd minimax polynomial
+// t * P(t^2) of degree 11 over the whole interval (fitted to atan on [0, 1]; 3.4e-7 there, 3.9e-7 evaluated in float32),
+// then the quadrant.  No octant fold: the fold t -> (t-1)/(t+1) past tan(pi/8) cost eight instructions (compare, two selects,
+// sub, add, the pi/4 add and select) against two more polynomial terms.  atan2(0, 0) = 0: mx = 0 gives t = 0 / FLT_MIN.
 // (Results only feed float32 observation/reward features that are compared at 1e-5.)
 __device__ __forceinline__ float atan2_fast(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
     const float mx = fmaxf(ax, ay), mn = fminf(ax, ay);
-    const bool big = mn > 0.41421356237f * mx;
-    const float num = big ? mn - mx : mn;
-    float den = big ? mn + mx : mx;
-    den = (mx == 0.f) ? 1.f : den;              // atan2(0, 0) = 0
-    const float t = num * __builtin_amdgcn_rcpf(den);
+    const float t = mn * __builtin_amdgcn_rcpf(fmaxf(mx, 1.17549435e-38f));
     const float z = t * t;
-    float pl = fmaf(8.05374449538e-2f, z, -1.38776856032e-1f);
-    pl = fmaf(pl, z, 1.99777106478e-1f);
-    pl = fmaf(pl, z, -3.33329491539e-1f);
+    float pl = fmaf(7.37447338e-3f, z, -3.55211943e-2f);
+    pl = fmaf(pl, z, 8.21691155e-2f);
+    pl = fmaf(pl, z, -1.33988619e-1f);
+    pl = fmaf(pl, z, 1.98618680e-1f);
+    pl = fmaf(pl, z, -3.33253950e-1f);
     float r = fmaf(pl * z, t, t);
-    r = big ? r + 0.78539816339744830962f : r;
     r = (ay > ax) ? 1.57079632679489661923f - r : r;
     r = (x < 0.f) ? kPi - r : r;
     return copysignf(r, y);
 }
 
-// The same reduction and polynomial with an IEEE division instead of v_rcp_f32: every operation is correctly rounded, so
+// The octant reduction and Cephes atanf polynomial on |t| <= tan(pi/8), with an IEEE division: every operation is correctly rounded, so
 // the CPU test oracle restates it bit for bit (its atan2_leg).  Used where an angle becomes STATE (the heading
 // a scripted body keeps for a whole leg); off the per-step path, so its cost does not matter.
 __device__ __forceinline__ float atan2_exact(float y, float x) {

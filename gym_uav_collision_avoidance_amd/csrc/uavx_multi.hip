@@ -451,6 +451,70 @@ __device__ __forceinline__ Neigh scan_neighbours_exact(float sq_sense, const Lan
     return r;
 }
 
+__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
+    uint32_t r;
+    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
+    return r;
+}
+
+// The same result for N = 4 with square roots of the two winners only (at N = 5 the kept third key and the inlined fallback
+// cost the fused multi-step kernel a wavefront per SIMD).  The visits keep the three smallest SQUARED
+// distances s1 <= s2 <= s3 (out of range: +inf), ties -> lower index (ascending visits, strict compares), which is the
+// order by (s, index).  sqrtf is monotone, so the reference's order by (float32 distance, index) (AG:52-62) can differ from it
+// only where two roots are EQUAL: for the first two that is decided here exactly (equal roots -> lower index first); the third
+// can only displace the second if its root equals the second's, which needs s3 within a few ulps of s2 (equal roots of s and
+// s' need |s - s'| < 2^-22 s, at most four ulps of s): any lane with s3 - s2 <= 8 ulps sends its wavefront through the exact
+// scan (never on random layouts; symmetric ones such as reset(circular=True) take it).  Bit-identical to scan_neighbours_exact.
+template <int NT, bool STEP, class LDS>
+__device__ __forceinline__ Neigh scan_neighbours_sq(float sq_sense, const LaneMap &m, const LDS &lds, float nx, float ny) {
+    static_assert(NT == 4, "three other agents");
+    const float4 *row = &lds.pos[m.rbase];
+    constexpr uint32_t kInfBits = 0x7f800000u;
+    uint32_t s1 = kInfBits, s2 = kInfBits, s3 = kInfBits;
+    float step_min = INFINITY;
+    int j1 = -1, j2 = -1;
+    constexpr int M = NT - 1;
+    float4 q[M];
+    int js[M];
+#pragma unroll
+    for (int k = 0; k < M; k++) {   // all LDS reads in front of the first use
+        js[k] = k + (k >= m.i ? 1 : 0);
+        q[k] = row[js[k]];
+    }
+#pragma unroll
+    for (int k = 0; k < M; k++) {
+        const int j = js[k];
+        const float dxn = q[k].z - nx, dyn = q[k].w - ny;   // target_agent.location - self.location (AG:51)
+        const float ax = dxn * dxn, ay = dyn * dyn;
+        const float sn0 = ax + ay;
+        if (STEP) {
+            const float dxo = q[k].x - nx, dyo = q[k].y - ny;
+            const float bx = dxo * dxo, by = dyo * dyo;
+            const float so = bx + by;
+            step_min = fminf(step_min, (j < m.i) ? sn0 : so);   // j<i already moved this step, j>i not yet; d_sense below
+        }
+        // AG:52 (NaN: out).  Non-negative floats and +inf order like their bit patterns: the three smallest are kept with
+        // integer min / median (fminf / fmaxf would canonicalise every operand first)
+        const uint32_t sn = (sn0 < sq_sense) ? __float_as_uint(sn0) : kInfBits;
+        const bool lt1 = sn < s1, lt2 = sn < s2;
+        j2 = lt1 ? j1 : (lt2 ? j : j2);
+        j1 = lt1 ? j : j1;
+        s3 = med3_u32(s2, s3, sn);
+        s2 = med3_u32(s1, s2, sn);
+        s1 = min(s1, sn);
+    }
+    Neigh r;
+    r.step_sq_min = (step_min < sq_sense) ? step_min : INFINITY;
+    r.d1 = sqrt_rn(__uint_as_float(s1));   // +inf stays +inf
+    r.d2 = sqrt_rn(__uint_as_float(s2));
+    const bool swap = r.d1 == r.d2 && j2 < j1;   // equal roots: lower index first (both in range: j2 >= 0)
+    r.j1 = swap ? j2 : j1;
+    r.j2 = swap ? j1 : j2;
+    const bool near_tie = m.active && s3 < kInfBits && s3 - s2 <= 8u;
+    if (__builtin_expect(__any(near_tie), 0)) return scan_neighbours_exact<NT, STEP>(sq_sense, m, lds, nx, ny);
+    return r;
+}
+
 // Same result for N > 5 (and the N = 8 specialisation) at about half the per-neighbour cost: the scan keeps the
 // three smallest KEYS, key = (bits of the squared distance with the low 6 bits replaced by a name of the neighbour), with
 // one v_min_u32 + two v_med3_u32 per neighbour instead of a compare/select insertion of (distance, index)
@@ -468,15 +532,13 @@ __device__ __forceinline__ Neigh scan_neighbours_exact(float sq_sense, const Lan
 #ifdef UAVX_STAMPS
 __shared__ int g_dbg_fallback;   // diagnostic build: this workgroup took the exact scan / the finish() branch (bits 0 / 1)
 #endif
-__device__ __forceinline__ uint32_t med3_u32(uint32_t a, uint32_t b, uint32_t c) {
-    uint32_t r;
-    asm("v_med3_u32 %0, %1, %2, %3" : "=v"(r) : "v"(a), "v"(b), "v"(c));
-    return r;
-}
 
-template <int NT, bool STEP, class LDS>
+// SQ: the one-step kernel at N = 4 takes scan_neighbours_sq (the fused kernels keep the exact scan: there the inlined fallback
+// cost registers -- step_k_kernel<4> 69 -> 78 VGPRs with two scalars spilled into VGPR lanes, step_ex_kernel<4> 50 -> 57)
+template <int NT, bool STEP, class LDS, bool SQ = false>
 __device__ __forceinline__ Neigh scan_neighbours(float sq_sense, const LaneMap &m, const LDS &lds, float nx,
                                                  float ny) {
+    if (SQ && NT == 4) return scan_neighbours_sq<4, STEP>(sq_sense, m, lds, nx, ny);
     if (NT != 0 && NT <= 5) return scan_neighbours_exact<NT, STEP>(sq_sense, m, lds, nx, ny);
     const int N = NT ? NT : m.nslots;
     if (NT == 0 && N <= 5) return scan_neighbours_exact<NT, STEP>(sq_sense, m, lds, nx, ny);  // <= 4 others: nothing to save
@@ -640,10 +702,10 @@ __device__ __forceinline__ void assemble_obs(const MultiParams &p, const WorldLi
     const int i1 = m.rbase + (has1 ? nb.j1 : 0), i2 = m.rbase + (has2 ? nb.j2 : 0);
     const float4 q1 = lds.pos[i1], q2 = lds.pos[i2];
     const float t1 = lds.theta[i1], t2 = lds.theta[i2];
-    const float b1 = wrap_pi(atan2_fast(q1.w - ny, q1.z - nx) - theta) * kInvPi;  // MUW:78-81
-    const float b2 = wrap_pi(atan2_fast(q2.w - ny, q2.z - nx) - theta) * kInvPi;  // MUW:88-91
-    const float h1 = wrap_pi(t1 - theta) * kInvPi;                                // MUW:82-85
-    const float h2 = wrap_pi(t2 - theta) * kInvPi;                                // MUW:92-95
+    const float b1 = wrap_unit(atan2_fast(q1.w - ny, q1.z - nx) - theta);  // MUW:78-81
+    const float b2 = wrap_unit(atan2_fast(q2.w - ny, q2.z - nx) - theta);  // MUW:88-91
+    const float h1 = wrap_unit(t1 - theta);                                // MUW:82-85
+    const float h2 = wrap_unit(t2 - theta);                                // MUW:92-95
     o[4] = has1 ? nb.d1 * w.inv_sense : 1.f;                                      // MUW:77
     o[5] = has1 ? b1 : 1.f;
     o[6] = has1 ? h1 : 0.f;
@@ -764,7 +826,7 @@ __device__ __forceinline__ void stage_bodies(const MultiParams &p, const LaneMap
 //   frozen: the env was re-initialised by this call (auto-reset); the agent only observes.
 //   EXT: env_steps / ep_draw = the env's step count before this step and the episode index its reset drew with
 //        (scripted bodies); frozen envs had their bodies' rows staged by the reset path.
-template <int NT, bool EXT, class LDS, bool LATEW = false>
+template <int NT, bool EXT, class LDS, bool LATEW = false, bool SQ = false>   // SQ: see scan_neighbours
 __device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &m, LDS &lds, AgentRegs &s, double ax,
                                            double ay, int evaluate, float o[10], float &rew, uint32_t &done_out,
                                            uint32_t &reach_ev, uint32_t &coll_ev, bool frozen = false,
@@ -793,7 +855,7 @@ __device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &
     }
     if (EXT && p.B > 0) stage_bodies<true, LDS, LATEW>(p, m, lds, s.flags, frozen, env_steps, ep_draw);
     group_sync<LDS::kW>();
-    const Neigh nb = scan_neighbours<NT, true>(sq_sense, m, lds, s.x, s.y);
+    const Neigh nb = scan_neighbours<NT, true, LDS, SQ>(sq_sense, m, lds, s.x, s.y);
     const WorldLims w = world_lims<EXT>(p, s.flags);
 
     // reward shaping, MUW:188-195 (float32, reciprocals instead of divisions; |error| << 1e-5)
@@ -881,9 +943,16 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
     static_assert(T == 1 || !EXT, "tiles: the plain variants only");
     __shared__ LDS lds;
     const uint32_t tile = T > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave)) : 0u;   // (a scalar)
+    // 4 UAVs, one step: state rows through buffer resources (16 scalar registers for the four of them; the other variants have none
+    // to spare) and the squared-distance neighbour scan (scan_neighbours)
+    constexpr bool BUF = NT == 4 && !EXT && T == 1;
     float2 *const pos_b = reinterpret_cast<float2 *>(slab);
     double2 *const vel_b = reinterpret_cast<double2 *>(slab + off_vel);
     Goal *const goal_b = reinterpret_cast<Goal *>(slab + off_goal);
+    const uint32_t nslot = num_envs * n_agents;   // E*N < 2^26 (uavx_create): every byte offset below fits 32 bits
+    const rsrc_t r_act = make_rsrc(actions, nslot * (ACT64 ? 16u : 8u));
+    const rsrc_t r_pos = make_rsrc(slab, nslot * 8u), r_vel = make_rsrc(slab + off_vel, nslot * 16u);
+    const rsrc_t r_goal = make_rsrc(slab + off_goal, nslot * 16u);
     const uint32_t wave_id = blockIdx.x * T + tile;
     const LaneMap m = lane_map_from<NT, EXT, W>(num_envs, (int)n_agents, (int)envs_per_group, (int)magic, (int)nslots, wave_id,
                                                 T > 1 ? threadIdx.x % kWave : threadIdx.x, tile);
@@ -900,25 +969,53 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
             rec = reinterpret_cast<const uint4 *>(slab + off_rec)[el];
             wave_count = reinterpret_cast<const uint32_t *>(slab + off_wsteps)[wave_id];
         }
-        load_action<ACT64>(actions, al, ax, ay);
-        const float2 d = pos_b[al];
-        const double2 v = vel_b[al];
-        const Goal g = goal_b[al];
-        __builtin_amdgcn_sched_barrier(0);
-        s.x = d.x; s.y = d.y; s.vx = v.x; s.vy = v.y;
-        s.tx = g.tx; s.ty = g.ty; s.init_d = g.init_d; s.flags = g.flags;
+        // BUF: buffer loads, one 32-bit lane offset per row size on top of the scalar bases (a global load needs a 64-bit
+        // address per lane and array)
+        if (!BUF) {
+            load_action<ACT64>(actions, al, ax, ay);
+            const float2 d = pos_b[al];
+            const double2 v = vel_b[al];
+            const Goal g = goal_b[al];
+            __builtin_amdgcn_sched_barrier(0);
+            s.x = d.x; s.y = d.y; s.vx = v.x; s.vy = v.y;
+            s.tx = g.tx; s.ty = g.ty; s.init_d = g.init_d; s.flags = g.flags;
+        } else {
+            if (ACT64) {
+                const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(r_act, al * 16u, 0, 0);
+                ax = __hiloint2double(c.y, c.x); ay = __hiloint2double(c.w, c.z);
+            } else {
+                const u32x2 c = __builtin_amdgcn_raw_buffer_load_b64(r_act, al * 8u, 0, 0);
+                ax = (double)__uint_as_float(c.x); ay = (double)__uint_as_float(c.y);
+            }
+            const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(r_pos, al * 8u, 0, 0);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r_vel, al * 16u, 0, 0);
+            const u32x4 g = __builtin_amdgcn_raw_buffer_load_b128(r_goal, al * 16u, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            s.x = __uint_as_float(d.x); s.y = __uint_as_float(d.y);
+            s.vx = __hiloint2double(v.y, v.x); s.vy = __hiloint2double(v.w, v.z);
+            s.tx = __uint_as_float(g.x); s.ty = __uint_as_float(g.y); s.init_d = __uint_as_float(g.z); s.flags = g.w;
+        }
         s.prev_d = natural_prev_d(s.flags, s.x, s.y, s.tx, s.ty);
         if (m.active && (s.flags & kFlagPrevOvr)) s.prev_d = p.prev_ovr[m.a];  // rare: only after a caller poked the state
     }
     const uint32_t flags_in = s.flags;
     float o[10], rew;
     uint32_t dn, re, ce;
-    step_agent<NT, EXT, LDS, false>(p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, false, wave_count - rec.x,
+    step_agent<NT, EXT, LDS, false, BUF>(p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, false, wave_count - rec.x,
                                     ((rec.y & ~kRecEnded) - 1u) & ~kRecEnded);
     if (m.active) {
-        if (!(EXT && (flags_in & kFlagInactive))) store_agent(p, pos_b, vel_b, goal_b, m.a, s, flags_in);
-        rew_out[m.a] = rew;
-        done_out[m.a] = (uint8_t)dn;
+        if (!BUF) {
+            if (!(EXT && (flags_in & kFlagInactive))) store_agent(p, pos_b, vel_b, goal_b, m.a, s, flags_in);
+            rew_out[m.a] = rew;
+            done_out[m.a] = (uint8_t)dn;
+        } else {   // store_agent() through the buffer resources of the loads
+            store16_wt(r_vel, m.a * 16u, make_double2(s.vx, s.vy));
+            const u32x2 d = {__float_as_uint(s.x), __float_as_uint(s.y)};
+            __builtin_amdgcn_raw_buffer_store_b64(d, r_pos, m.a * 8u, 0, 0);
+            if (s.flags != flags_in) __builtin_amdgcn_raw_buffer_store_b32(s.flags, r_goal, m.a * 16u + 12u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), make_rsrc(rew_out, nslot * 4u), m.a * 4u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)dn, make_rsrc(done_out, nslot), m.a, 0, 0);
+        }
         if (re) atomicAdd(&p.reach[m.e], 1u);                // MUW:221
         if (ce) atomicAdd(&p.coll[m.e], 1u);                 // MUW:209
         if (!(fabsf(rew) < INFINITY)) atomicAdd(&p.nonfin[m.e], 1u);   // the tripwire of test_ddpg_multi.py:114-130, per env
