@@ -1,5 +1,5 @@
-"""ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h), the fused actor-inference, critic
-and TD-target kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+"""ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h), the fused
+actor-inference, critic, TD-target and critic-gradient kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
 that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
 missing library or device raises."""
 import ctypes
@@ -12,6 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "actor_csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_actor.h")
 CRITIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic.h")
+GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic_grad.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -28,18 +29,24 @@ CRITIC_SYMBOLS = ("uavx_critic_version", "uavx_critic_strerror", "uavx_critic_cr
                   "uavx_critic_set_split_rows", "uavx_critic_pack", "uavx_critic_q", "uavx_critic_target")
 CRITIC_ABI_VERSION = 1
 SPLIT_ROWS = 16384      # UAVX_CRITIC_SPLIT_ROWS: batches below it run the small-batch variant
+# every symbol include/uavx_critic_grad.h declares
+GRAD_SYMBOLS = ("uavx_critic_grad_version", "uavx_critic_grad_workspace_bytes", "uavx_critic_grad")
+GRAD_ABI_VERSION = 1
+GRAD_MSE, GRAD_L1 = 0, 1
+GRAD_MAX_ROWS = 262144  # UAVX_CRITIC_GRAD_MAX_ROWS
 
 _lib_handle = None
 
 
 def _sources():
     import glob
-    return sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp"))) + [HEADER, CRITIC_HEADER]
+    return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
+            + [HEADER, CRITIC_HEADER, GRAD_HEADER])
 
 
 def source_hash():
     """sha256 over the code (comments and whitespace dropped, _lib._code_only) of actor_csrc/*.hip, *.hpp,
-    include/uavx_actor.h and include/uavx_critic.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS
+    include/uavx_actor.h, include/uavx_critic.h and include/uavx_critic_grad.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS
     override; 16 hex digits."""
     import hashlib
     h = hashlib.sha256()
@@ -120,6 +127,13 @@ def load():
     L.uavx_critic_pack.argtypes = [vp] + [vp] * 12 + [vp]
     L.uavx_critic_q.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp]
     L.uavx_critic_target.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, f32, f32, f32, vp, i64, vp, i64, vp]
+    L.uavx_critic_grad_version.restype = i32
+    if L.uavx_critic_grad_version() != GRAD_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks critic-gradient ABI version {L.uavx_critic_grad_version()}, this package "
+                           f"binds {GRAD_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_critic_grad_workspace_bytes.argtypes = [vp, i64, ctypes.POINTER(i64)]
+    L.uavx_critic_grad.argtypes = [vp, i32, ctypes.POINTER(vp), vp, i64, i64, vp, i64, vp, i64, ctypes.POINTER(vp), vp, vp,
+                                   i64, vp]
     _lib_handle = L
     return L
 

@@ -1,9 +1,11 @@
-// Definitions shared by the actor (uavx_actor.hip) and critic (uavx_critic.hip) translation units of libuavx_actor.so:
-// the packed-weight layout of one 3-layer MLP, the MFMA k order, the activations and the actor handle itself.
+// Definitions shared by the actor (uavx_actor.hip), critic (uavx_critic.hip) and critic-gradient (uavx_critic_grad.hip)
+// translation units of libuavx_actor.so: the packed-weight layout of one 3-layer MLP, the MFMA k order, the activations
+// and the actor and critic handles themselves.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uavx_actor.h"
+#include "../../include/uavx_critic.h"
 
 namespace uavx_actor_k {
 
@@ -78,5 +80,14 @@ struct uavx_actor {
     uavx_actor_k::Layout L;
     float *bias;        // device: L.bias_floats floats, then the fragments
     void *frags;
+    bool packed;
+};
+
+struct uavx_critic {
+    int kind, prec, h1, h2, towers;
+    uavx_actor_k::Layout L;   // of one tower
+    float *bias;        // device: towers x L.bias_floats floats, then towers x L.frag_elems fragment elements
+    void *frags;
+    int64_t split_rows;
     bool packed;
 };

@@ -329,15 +329,6 @@ __global__ __launch_bounds__(S == 1 ? WG : 64 * S, WPS) void critic_fwd(Args a) 
 
 using namespace uavx_critic_k;
 
-struct uavx_critic {
-    int kind, prec, h1, h2, towers;
-    Layout L;           // of one tower
-    float *bias;        // device: towers x L.bias_floats floats, then towers x L.frag_elems fragment elements
-    void *frags;
-    int64_t split_rows;
-    bool packed;
-};
-
 namespace {
 
 typedef void (*fwd_fn)(Args);

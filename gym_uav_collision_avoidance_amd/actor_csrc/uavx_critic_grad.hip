@@ -1,0 +1,526 @@
+// Critic-loss gradients (include/uavx_critic_grad.h): the forward with saved activations, the MSE / L1 loss and the
+// backward of the learners' critic update, in three launches.  DESIGN.md §14.
+//
+// All products run on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fmaf chain).  Lane l = 16·g + c of a wave holds
+// A[m = c][k = g] and B[k = g][n = c]; the accumulator element ii holds C[m = 4g + ii][n = c].
+//
+//   1. grad_rows     one workgroup (4 waves) per 16-row block and tower; rows are MFMA columns, units MFMA rows.
+//                    Layer 1 (f64, rounded once) into LDS and to the workspace, for dW2; z2ᵀ = W2·h1ᵀ with wave w
+//                    taking the 16-unit blocks j ≡ w (mod 4), each 16-wide k block's MFMA chain added up in f64, z2
+//                    written to the workspace; q summed over units and waves in a fixed order;
+//                    dq per row; then per unit block again: δ2 = dq·w3 ⊙ act′(z2) over z2 in the workspace, and
+//                    δ1ᵀ += W2ᵀ·δ2ᵀ straight from the δ2 accumulator (its k order is the unit order of the block).  The
+//                    four waves' δ1 are summed through LDS in wave order.  The block's sums over its 16 rows of the
+//                    small gradients (W1, b1, b2, W3, b3) and of the loss go to a per-block partial row (f64).
+//   2. grad_weights  one wave per job: a 64 x 64 tile of dW2 = Σ_rows δ2ᵀ·h1 over one split-K slice of rows, or a
+//                    256-column slice of the per-block partial rows summed over the slice's blocks (f64).
+//   3. grad_combine  one thread per output element: the split-K slices summed in slice order (f64), rounded once to f32
+//                    and written in torch layout; the loss divided by the row count.
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+#include "../../include/uavx_critic_grad.h"
+#include "uavx_actor_impl.hpp"
+
+namespace uavx_critic_grad_k {
+
+using uavx_actor_k::act;
+using uavx_actor_k::f32x4;
+
+constexpr int OBS = 10, IN = 12, WG = 256, WAVES = WG / 64;
+
+__device__ inline f32x4 mma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
+
+// torch's backward of the activation, given the pre-activation z and the incoming gradient d:
+// relu: threshold_backward (z <= 0 gives 0; NaN passes), leaky_relu(0.01): z > 0 ? d : d·0.01
+template <bool LEAKY>
+__device__ inline float act_bwd(float z, float d) {
+    if constexpr (LEAKY) return z > 0.f ? d : d * 0.01f;
+    else return z <= 0.f ? 0.f : d;
+}
+
+// sum over the 16 lanes of a lane group (c = lane & 15) by butterfly: every lane ends with the same bits
+__device__ inline double sum16(double v) {
+#pragma unroll
+    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);
+    return v;
+}
+
+// offsets inside a per-block partial row (and inside the small-gradient slices): W1 [h1][12], b1, b2, W3, b3, loss
+struct Small {
+    int w1, b1, b2, w3, b3, loss, n;
+};
+__host__ __device__ inline Small small_layout(int h1, int h2) {
+    Small s;
+    s.w1 = 0;
+    s.b1 = 12 * h1;
+    s.b2 = 13 * h1;
+    s.w3 = s.b2 + h2;
+    s.b3 = s.w3 + h2;
+    s.loss = s.b3 + 1;
+    s.n = s.loss + 1;
+    return s;
+}
+
+struct RowArgs {
+    const float *W1[2], *b1[2], *W2[2], *b2[2], *W3[2], *b3[2];
+    const float *state, *action, *y;
+    int64_t rows, s_stride, a_stride, y_stride;
+    float *h1ws, *d2ws;                // tower t at + t * *_tower
+    double *pws;
+    int64_t h1_tower, d2_tower, p_tower;
+    int h1, h2, nb2, lp, loss;
+    double mse_scale;                  // 2.0 / rows
+    float dq_scale;                    // L1: 1.f / rows
+};
+
+template <bool LEAKY, int NB1>
+__global__ __launch_bounds__(WG) void grad_rows(RowArgs a) {
+    constexpr int N1 = 16 * NB1, HP = N1 + 4;
+    __shared__ float xs[16][IN];
+    __shared__ float h1s[16][HP];              // h1 of the block's rows; δ1 at the end
+    __shared__ f32x4 red[WAVES][NB1][64];      // each wave's δ1ᵀ accumulators
+    __shared__ double qs[WAVES][16];
+    __shared__ float ls[16];
+    __shared__ float dqs[16];
+    const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15, wave = tid >> 6;
+    const int t = blockIdx.y, h1 = a.h1, h2 = a.h2, ld2 = 16 * a.nb2;
+    const int64_t row0 = (int64_t)blockIdx.x * 16;
+    // tower t's parameters, selected without indexing the argument arrays by a run-time value (that goes to scratch)
+    const float *__restrict__ W1 = t ? a.W1[1] : a.W1[0], *__restrict__ b1 = t ? a.b1[1] : a.b1[0];
+    const float *__restrict__ W2 = t ? a.W2[1] : a.W2[0], *__restrict__ b2 = t ? a.b2[1] : a.b2[0];
+    const float *__restrict__ W3 = t ? a.W3[1] : a.W3[0], *__restrict__ b3 = t ? a.b3[1] : a.b3[0];
+    float *H1w = a.h1ws + t * a.h1_tower + row0 * N1;
+    float *D2w = a.d2ws + t * a.d2_tower + row0 * ld2;
+    double *P = a.pws + t * a.p_tower + (int64_t)blockIdx.x * a.lp;
+    const Small sl = small_layout(h1, h2);
+    const bool rin = row0 + c < a.rows;        // row c of the block is a real row
+
+    // ---- [state, action] of the block's rows (0 past the last row: nothing there is read)
+    if (tid < 16 * IN) {
+        const int r = tid / IN, k = tid % IN;
+        const int64_t row = row0 + r;
+        float v = 0.f;
+        if (row < a.rows) v = k < OBS ? a.state[row * a.s_stride + k] : a.action[row * a.a_stride + (k - OBS)];
+        xs[r][k] = v;
+    }
+    __syncthreads();
+
+    // ---- layer 1: h1 into LDS and the workspace; 0 for padded units and padded rows
+    for (int e = tid; e < 16 * N1; e += WG) {
+        const int r = e / N1, i = e % N1;
+        float h = 0.f;
+        if (i < h1 && row0 + r < a.rows) {
+            double z = b1[i];                  // in f64, rounded once
+#pragma unroll
+            for (int k = 0; k < IN; ++k) z += (double)W1[i * IN + k] * (double)xs[r][k];
+            h = act<LEAKY>((float)z);
+        }
+        h1s[r][i] = h;
+        H1w[(int64_t)r * N1 + i] = h;
+    }
+    __syncthreads();
+
+    // ---- pass 1: z2 of the wave's unit blocks into the workspace, q folded per lane (in f64: dq is the only per-row value
+    // every gradient scales with)
+    double qp = 0.0;
+    for (int jb = wave; jb < a.nb2; jb += WAVES) {
+        const int j = 16 * jb + c;             // this lane's A row
+        const bool jin = j < h2;
+        const float *w2 = W2 + (int64_t)(jin ? j : 0) * h1;
+        // each 16-wide k block is a 4-step fmaf chain of its own (rotating over four accumulators so that the MFMAs of
+        // neighbouring blocks overlap), added into f64: z2, and with it dq, is rounded once, not once per k step
+        f32x4 acc4[4];
+        double zd[4] = {0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int kb = 0; kb < NB1; ++kb) {
+            const f32x4 hv = *(const f32x4 *)&h1s[c][16 * kb + 4 * g];
+            f32x4 &acc = acc4[kb & 3];
+            acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii) {
+                const int k = 16 * kb + 4 * g + ii;
+                acc = mma(jin && (kb < NB1 - 1 || k < h1) ? w2[k] : 0.f, hv[ii], acc);   // h1 > 16·(NB1 − 1)
+            }
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii) zd[ii] += (double)acc[ii];
+        }
+        f32x4 z;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+            const int jj = 16 * jb + 4 * g + ii;
+            z[ii] = jj < h2 ? (float)(zd[ii] + (double)b2[jj]) : 0.f;
+            qp += (double)(jj < h2 ? W3[jj] : 0.f) * (double)act<LEAKY>(z[ii]);
+        }
+        *(f32x4 *)&D2w[(int64_t)c * ld2 + 16 * jb + 4 * g] = z;
+    }
+    qp += __shfl_xor(qp, 16);
+    qp += __shfl_xor(qp, 32);
+    if (g == 0) qs[wave][c] = qp;
+    __syncthreads();
+    if (tid < 16) {
+        const int64_t row = row0 + tid;
+        double q = qs[0][tid];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) q += qs[w][tid];
+        q += (double)b3[0];
+        float dq = 0.f, l = 0.f;
+        if (row < a.rows) {
+            const double dd = q - (double)a.y[row * a.y_stride];
+            const float d = (float)dd;
+            if (a.loss == UAVX_CRITIC_GRAD_MSE) {
+                dq = (float)(dd * a.mse_scale);   // mse_loss_backward: (q − y) · (2 / B), rounded once
+                l = (float)(dd * dd);
+            } else {
+                const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);   // torch.sign (0 for 0 and NaN)
+                dq = sg * a.dq_scale;         // mean then abs backward: sign(q − y) · (1 / B)
+                l = fabsf(d);
+            }
+        }
+        dqs[tid] = dq;
+        ls[tid] = l;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        double sd = 0.0, sl2 = 0.0;
+        for (int r = 0; r < 16; ++r) {
+            sd += dqs[r];
+            sl2 += ls[r];
+        }
+        P[sl.b3] = sd;
+        P[sl.loss] = sl2;
+    }
+
+    // ---- pass 2: δ2 over the workspace's z2, its column sums (b2) and those of dq·h2 (W3); δ1ᵀ += W2ᵀ·δ2ᵀ
+    const float dq = dqs[c];
+    f32x4 dacc[NB1];
+#pragma unroll
+    for (int ib = 0; ib < NB1; ++ib) dacc[ib] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int jb = wave; jb < a.nb2; jb += WAVES) {
+        f32x4 *zp = (f32x4 *)&D2w[(int64_t)c * ld2 + 16 * jb + 4 * g];
+        const f32x4 z = *zp;
+        f32x4 d2;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+            const int jj = 16 * jb + 4 * g + ii;
+            const float w3 = jj < h2 ? W3[jj] : 0.f;
+            d2[ii] = rin && jj < h2 ? act_bwd<LEAKY>(z[ii], dq * w3) : 0.f;
+            const double s2 = sum16(d2[ii]);
+            const double s3 = sum16(rin && jj < h2 ? (double)dq * (double)act<LEAKY>(z[ii]) : 0.0);
+            if (c == 0 && jj < h2) {
+                P[sl.b2 + jj] = s2;
+                P[sl.w3 + jj] = s3;
+            }
+        }
+        *zp = d2;
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+            const int j = 16 * jb + 4 * g + ii;
+            const float *w2 = W2 + (int64_t)(j < h2 ? j : 0) * h1;
+#pragma unroll
+            for (int ib = 0; ib < NB1; ++ib) {
+                const int i = 16 * ib + c;
+                dacc[ib] = mma(j < h2 && (ib < NB1 - 1 || i < h1) ? w2[i] : 0.f, d2[ii], dacc[ib]);
+            }
+        }
+    }
+#pragma unroll
+    for (int ib = 0; ib < NB1; ++ib) red[wave][ib][lane] = dacc[ib];
+    __syncthreads();
+    // δ1 = (Σ_waves, in wave order) ⊙ act′(z1), over h1 in LDS (h1 > 0 exactly when z1 > 0; a NaN stays a NaN)
+    for (int ib = wave; ib < NB1; ib += WAVES) {
+        f32x4 s = red[0][ib][lane];
+#pragma unroll
+        for (int w = 1; w < WAVES; ++w) s += red[w][ib][lane];
+#pragma unroll
+        for (int ii = 0; ii < 4; ++ii) {
+            const int i = 16 * ib + 4 * g + ii;
+            const float hv = h1s[c][i];
+            h1s[c][i] = rin && i < h1 ? act_bwd<LEAKY>(hv, s[ii]) : 0.f;
+        }
+    }
+    __syncthreads();
+    // W1, b1 over the block's 16 rows: one (unit, input) pair per thread step, rows in order
+    for (int e = tid; e < h1 * 13; e += WG) {
+        const int i = e / 13, k = e % 13;
+        double s = 0.0;
+        if (k < IN) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s += (double)h1s[r][i] * (double)xs[r][k];
+            P[sl.w1 + i * IN + k] = s;
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) s += h1s[r][i];
+            P[sl.b1 + i] = s;
+        }
+    }
+}
+
+struct WeightArgs {
+    const float *h1ws, *d2ws;
+    const double *pws;
+    int64_t h1_tower, d2_tower, p_tower;
+    float *part2;                      // [S][towers][h2][h1]
+    double *partp;                     // [S][towers][lp]
+    int64_t b16, kc;
+    int h1, n1, h2, nb2, lp, towers, S, tj, ti, pchunks;
+};
+
+__global__ __launch_bounds__(WG) void grad_weights(WeightArgs a) {
+    const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
+    int64_t job = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    const int64_t tiles = (int64_t)a.towers * a.tj * a.ti;
+    if (job < tiles * a.S) {
+        // ---- a 64 x 64 tile of dW2 over rows [s·kc, (s+1)·kc): A = δ2ᵀ (units x rows), B = h1 (rows x inputs)
+        const int s = (int)(job / tiles);
+        const int64_t rem = job % tiles;
+        const int t = (int)(rem / (a.tj * a.ti)), tile = (int)(rem % (a.tj * a.ti));
+        const int j0 = 64 * (tile / a.ti), i0 = 64 * (tile % a.ti), ld2 = 16 * a.nb2;
+        const float *D = a.d2ws + t * a.d2_tower, *H = a.h1ws + t * a.h1_tower;
+        const int64_t r_lo = s * a.kc, r_hi = r_lo + a.kc < a.b16 ? r_lo + a.kc : a.b16;
+        int jm[4], in_[4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            jm[m] = j0 + 16 * m + c;
+            in_[m] = i0 + 16 * m + c;
+        }
+        f32x4 acc[4][4];
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int64_t r = r_lo; r < r_hi; r += 4) {
+            const float *dr = D + (r + g) * ld2, *hr = H + (r + g) * a.n1;
+            float av[4], bv[4];
+#pragma unroll
+            for (int m = 0; m < 4; ++m) {
+                av[m] = jm[m] < a.h2 ? dr[jm[m]] : 0.f;
+                bv[m] = in_[m] < a.h1 ? hr[in_[m]] : 0.f;
+            }
+#pragma unroll
+            for (int m = 0; m < 4; ++m)
+#pragma unroll
+                for (int n = 0; n < 4; ++n) acc[m][n] = mma(av[m], bv[n], acc[m][n]);
+        }
+        float *out = a.part2 + ((int64_t)s * a.towers + t) * a.h2 * a.h1;
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii) {
+                const int j = j0 + 16 * m + 4 * g + ii;
+                if (j >= a.h2) continue;
+#pragma unroll
+                for (int n = 0; n < 4; ++n)
+                    if (in_[n] < a.h1) out[(int64_t)j * a.h1 + in_[n]] = acc[m][n][ii];
+            }
+        return;
+    }
+    job -= tiles * a.S;
+    const int64_t pjobs = (int64_t)a.towers * a.pchunks;
+    if (job >= pjobs * a.S) return;
+    // ---- 256 columns of the per-block partial rows summed over the blocks of slice s, in block order, in f64
+    const int s = (int)(job / pjobs);
+    const int t = (int)(job % pjobs / a.pchunks), chunk = (int)(job % a.pchunks);
+    const int e0 = 256 * chunk + 4 * lane;
+    if (e0 >= a.lp) return;
+    const int64_t w_lo = s * (a.kc / 16), w_end = (s + 1) * (a.kc / 16), nblk = a.b16 / 16;
+    const int64_t w_hi = w_end < nblk ? w_end : nblk;
+    const double *P = a.pws + t * a.p_tower + e0;
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int64_t w = w_lo; w < w_hi; ++w) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) acc[q] += P[w * a.lp + q];
+    }
+    double *out = a.partp + ((int64_t)s * a.towers + t) * a.lp + e0;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) out[q] = acc[q];
+}
+
+struct CombineArgs {
+    const float *part2;
+    const double *partp;
+    float *grads[12];
+    float *loss;
+    int64_t rows;
+    int h1, h2, lp, towers, S;
+};
+
+__global__ __launch_bounds__(WG) void grad_combine(CombineArgs a) {
+    const Small sl = small_layout(a.h1, a.h2);
+    const int64_t n2 = (int64_t)a.h2 * a.h1, per = n2 + sl.n;
+    const int64_t e = (int64_t)blockIdx.x * WG + threadIdx.x;
+    if (e >= a.towers * per) return;
+    const int t = (int)(e / per);
+    int64_t f = e % per;
+    double s = 0.0;
+    if (f < n2) {
+        for (int k = 0; k < a.S; ++k) s += (double)a.part2[((int64_t)k * a.towers + t) * n2 + f];
+        a.grads[6 * t + 2][f] = (float)s;
+        return;
+    }
+    f -= n2;
+    for (int k = 0; k < a.S; ++k) s += a.partp[((int64_t)k * a.towers + t) * a.lp + f];
+    if (f < sl.b1) a.grads[6 * t + 0][f] = (float)s;
+    else if (f < sl.b2) a.grads[6 * t + 1][f - sl.b1] = (float)s;
+    else if (f < sl.w3) a.grads[6 * t + 3][f - sl.b2] = (float)s;
+    else if (f < sl.b3) a.grads[6 * t + 4][f - sl.w3] = (float)s;
+    else if (f == sl.b3) a.grads[6 * t + 5][0] = (float)s;
+    else a.loss[t] = (float)(s / (double)a.rows);
+}
+
+}  // namespace uavx_critic_grad_k
+
+using namespace uavx_critic_grad_k;
+
+namespace {
+
+struct Plan {
+    int n1, nb2, lp, tj, ti, pchunks, S;
+    int64_t b16, kc, h1_tower, d2_tower, p_tower, off_d2, off_p, off_part2, off_partp, bytes;
+};
+
+int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
+
+Plan plan(const uavx_critic *h, int64_t rows) {
+    Plan p;
+    const int T = h->towers;
+    p.n1 = 16 * h->L.nb1;
+    p.nb2 = (h->h2 + 15) / 16;
+    p.lp = (small_layout(h->h1, h->h2).n + 3) & ~3;
+    p.tj = (h->h2 + 63) / 64;
+    p.ti = (h->h1 + 63) / 64;
+    p.pchunks = (p.lp + 255) / 256;
+    p.b16 = (rows + 15) / 16 * 16;
+    // split-K: about 8192 tile jobs, slices of at least 64 rows (a multiple of 16: whole row blocks)
+    const int64_t tiles = (int64_t)T * p.tj * p.ti, by_rows = (p.b16 + 63) / 64;
+    int64_t S = 8192 / tiles;
+    if (S < 1) S = 1;
+    if (S > by_rows) S = by_rows;
+    p.kc = ((p.b16 + S - 1) / S + 15) / 16 * 16;
+    p.S = (int)((p.b16 + p.kc - 1) / p.kc);
+    p.h1_tower = p.b16 * p.n1;
+    p.d2_tower = p.b16 * 16 * p.nb2;
+    p.p_tower = p.b16 / 16 * p.lp;
+    p.off_d2 = align256(T * p.h1_tower * 4);
+    p.off_p = p.off_d2 + align256(T * p.d2_tower * 4);
+    p.off_part2 = p.off_p + align256(T * p.p_tower * 8);
+    p.off_partp = p.off_part2 + align256((int64_t)p.S * T * h->h2 * h->h1 * 4);
+    p.bytes = p.off_partp + align256((int64_t)p.S * T * p.lp * 8);
+    return p;
+}
+
+typedef void (*rows_fn)(RowArgs);
+
+int check_handle(const uavx_critic *h, int64_t rows) {
+    if (!h || rows < 1 || rows > UAVX_CRITIC_GRAD_MAX_ROWS) return UAVX_CRITIC_ERR_INVALID_ARG;
+    if (h->prec != UAVX_CRITIC_F32) return UAVX_CRITIC_ERR_UNSUPPORTED;
+    if (h->L.nb1 != (h->kind == UAVX_CRITIC_DDPG ? 25 : 16)) return UAVX_CRITIC_ERR_UNSUPPORTED;
+    return UAVX_CRITIC_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavx_critic_grad_version(void) { return UAVX_CRITIC_GRAD_VERSION; }
+
+int uavx_critic_grad_workspace_bytes(const uavx_critic *h, int64_t rows, int64_t *bytes) {
+    if (!bytes) return UAVX_CRITIC_ERR_INVALID_ARG;
+    *bytes = 0;
+    const int rc = check_handle(h, rows);
+    if (rc != UAVX_CRITIC_OK) return rc;
+    *bytes = plan(h, rows).bytes;
+    return UAVX_CRITIC_OK;
+}
+
+int uavx_critic_grad(const uavx_critic *h, int loss, const float *const *params, const float *state, int64_t rows,
+                     int64_t s_stride, const float *action, int64_t a_stride, const float *y, int64_t y_stride,
+                     float *const *grads, float *loss_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!h || !params || !grads || rows < 1 || s_stride < OBS || a_stride < 2 || y_stride < 1)
+        return UAVX_CRITIC_ERR_INVALID_ARG;
+    if (loss != UAVX_CRITIC_GRAD_MSE && loss != UAVX_CRITIC_GRAD_L1) return UAVX_CRITIC_ERR_INVALID_ARG;
+    if (!state || !action || !y || !loss_out || !workspace || ((uintptr_t)workspace & 15)) return UAVX_CRITIC_ERR_INVALID_ARG;
+    const int rc = check_handle(h, rows);
+    if (rc != UAVX_CRITIC_OK) return rc;
+    const int T = h->towers;
+    for (int i = 0; i < 6 * T; ++i)
+        if (!params[i] || !grads[i]) return UAVX_CRITIC_ERR_INVALID_ARG;
+    const Plan p = plan(h, rows);
+    if (workspace_bytes < p.bytes) return UAVX_CRITIC_ERR_INVALID_ARG;
+    char *ws = (char *)workspace;
+    const hipStream_t st = (hipStream_t)stream;
+
+    RowArgs ra{};
+    for (int t = 0; t < T; ++t) {
+        ra.W1[t] = params[6 * t + 0];
+        ra.b1[t] = params[6 * t + 1];
+        ra.W2[t] = params[6 * t + 2];
+        ra.b2[t] = params[6 * t + 3];
+        ra.W3[t] = params[6 * t + 4];
+        ra.b3[t] = params[6 * t + 5];
+    }
+    ra.state = state;
+    ra.action = action;
+    ra.y = y;
+    ra.rows = rows;
+    ra.s_stride = s_stride;
+    ra.a_stride = a_stride;
+    ra.y_stride = y_stride;
+    ra.h1ws = (float *)ws;
+    ra.d2ws = (float *)(ws + p.off_d2);
+    ra.pws = (double *)(ws + p.off_p);
+    ra.h1_tower = p.h1_tower;
+    ra.d2_tower = p.d2_tower;
+    ra.p_tower = p.p_tower;
+    ra.h1 = h->h1;
+    ra.h2 = h->h2;
+    ra.nb2 = p.nb2;
+    ra.lp = p.lp;
+    ra.loss = loss;
+    ra.mse_scale = 2.0 / (double)rows;
+    ra.dq_scale = 1.f / (float)rows;
+    const rows_fn fr = h->kind == UAVX_CRITIC_DDPG ? grad_rows<true, 25> : grad_rows<false, 16>;
+    hipLaunchKernelGGL(fr, dim3((unsigned)(p.b16 / 16), (unsigned)T), dim3(WG), 0, st, ra);
+    if (hipGetLastError() != hipSuccess) return UAVX_CRITIC_ERR_HIP;
+
+    WeightArgs wa{};
+    wa.h1ws = ra.h1ws;
+    wa.d2ws = ra.d2ws;
+    wa.pws = ra.pws;
+    wa.h1_tower = p.h1_tower;
+    wa.d2_tower = p.d2_tower;
+    wa.p_tower = p.p_tower;
+    wa.part2 = (float *)(ws + p.off_part2);
+    wa.partp = (double *)(ws + p.off_partp);
+    wa.b16 = p.b16;
+    wa.kc = p.kc;
+    wa.h1 = h->h1;
+    wa.n1 = p.n1;
+    wa.h2 = h->h2;
+    wa.nb2 = p.nb2;
+    wa.lp = p.lp;
+    wa.towers = T;
+    wa.S = p.S;
+    wa.tj = p.tj;
+    wa.ti = p.ti;
+    wa.pchunks = p.pchunks;
+    const int64_t jobs = ((int64_t)T * p.tj * p.ti + (int64_t)T * p.pchunks) * p.S;
+    hipLaunchKernelGGL(grad_weights, dim3((unsigned)((jobs + WAVES - 1) / WAVES)), dim3(WG), 0, st, wa);
+    if (hipGetLastError() != hipSuccess) return UAVX_CRITIC_ERR_HIP;
+
+    CombineArgs ca{};
+    ca.part2 = wa.part2;
+    ca.partp = wa.partp;
+    for (int i = 0; i < 6 * T; ++i) ca.grads[i] = grads[i];
+    ca.loss = loss_out;
+    ca.rows = rows;
+    ca.h1 = h->h1;
+    ca.h2 = h->h2;
+    ca.lp = p.lp;
+    ca.towers = T;
+    ca.S = p.S;
+    const int64_t n = (int64_t)T * ((int64_t)h->h2 * h->h1 + small_layout(h->h1, h->h2).n);
+    hipLaunchKernelGGL(grad_combine, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, st, ca);
+    return hipGetLastError() == hipSuccess ? UAVX_CRITIC_OK : UAVX_CRITIC_ERR_HIP;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
 """FusedCritic and FusedTarget: the no-grad forward blocks of the reference's learners as ONE HIP launch each
-(libuavx_actor.so, include/uavx_critic.h) instead of a chain of torch layers and element-wise kernels.
+(libuavx_actor.so, include/uavx_critic.h) instead of a chain of torch layers and element-wise kernels; FusedCriticLoss: the
+gradient of the learners' critic loss in three launches (include/uavx_critic_grad.h), written into .grad.
 
     critic = FusedCritic.from_module(critic_target)                # TwinQ, TD3TwinQ or DDPGCritic
     q1, q2 = critic.q(state, action)                               # what the module's forward returns
@@ -240,3 +241,112 @@ class FusedTarget:
         for h in self._owned:
             h.close()
         self._owned = []
+
+
+_LOSSES = {"mse": _actor_lib.GRAD_MSE, "l1": _actor_lib.GRAD_L1}
+_DEFAULT_LOSS = {_actor_lib.SAC: "mse", _actor_lib.TD3: "mse", _actor_lib.DDPG: "l1"}
+
+
+class FusedCriticLoss:
+    """The gradient of the learners' critic loss (include/uavx_critic_grad.h, three HIP launches) written into the critic's
+    .grad, in place of `zero_grad(); loss.backward()`; the optimiser step stays torch's:
+
+        closs = FusedCriticLoss(critic)           # TwinQ / TD3TwinQ / DDPGCritic (f32, on a GPU) or an f32 FusedCritic
+        l1, l2 = closs.backward(s, a, y)          # SAC / TD3: mse_loss(q1, y) + mse_loss(q2, y); DDPG: one L1 loss
+        critic_optim.step()
+        closs.reserve(rows)                       # sizes the workspace before a graph capture
+
+    loss: "mse" (sac.py, td3.py), "l1" (ddpg.py:68) or None for the learner's own.  The call reads the module's LIVE
+    parameters when the kernels run (no refresh(): an optimiser step is seen by the next call), and leaves the packed
+    snapshot of a FusedCritic untouched.  Inputs must be float32 on the module's device; anything else raises."""
+
+    def __init__(self, critic, loss=None):
+        if isinstance(critic, FusedCritic):
+            fc, self._owned = critic, None
+        elif isinstance(critic, (TwinQ, TD3TwinQ, DDPGCritic)):
+            fc = None
+        else:
+            raise TypeError(f"uavx: FusedCriticLoss takes a TwinQ, TD3TwinQ, DDPGCritic or FusedCritic, not "
+                            f"{type(critic).__name__}")
+        module = fc.module if fc is not None else critic
+        kind = (_actor_lib.SAC if isinstance(module, TwinQ) else _actor_lib.TD3 if isinstance(module, TD3TwinQ)
+                else _actor_lib.DDPG)
+        if loss is None:
+            loss = _DEFAULT_LOSS[kind]
+        if loss not in _LOSSES:
+            raise ValueError(f"uavx: loss must be one of {sorted(_LOSSES)} or None, not {loss!r}")
+        if fc is None:
+            w = next(module.parameters())
+            if w.device.type != "cuda":
+                raise ValueError(f"uavx: FusedCriticLoss needs the module on a GPU (cuda:N), its parameters are on {w.device}")
+            fc = FusedCritic.from_module(module)
+            self._owned = fc
+        self.critic, self.module, self.kind, self.device = fc, module, fc.kind, fc.device
+        self.loss = loss
+        self._lib = fc._lib
+        self._params = [p for lin in fc._layers for p in (lin.weight, lin.bias)]
+        # persistent .grad buffers, assigned to a parameter whose .grad is missing or unusable (no allocation per call)
+        self._gbuf = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self._params]
+        self._loss = torch.zeros(fc.towers, dtype=torch.float32, device=self.device)
+        self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._gptrs = (ctypes.c_void_p * 12)()
+        self._pptrs = (ctypes.c_void_p * 12)()
+
+    def workspace_bytes(self, rows):
+        n = ctypes.c_int64()
+        rc = self._lib.uavx_critic_grad_workspace_bytes(self.critic._h, int(rows), ctypes.byref(n))
+        _actor_lib.check_critic(rc, f"uavx_critic_grad_workspace_bytes({rows})")
+        return n.value
+
+    def reserve(self, rows):
+        """Grows the workspace to what `rows` rows need (a graph capture cannot allocate it)."""
+        need = self.workspace_bytes(rows)
+        if self._ws.numel() < need:
+            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self
+
+    def _grads(self):
+        out = []
+        for p, buf in zip(self._params, self._gbuf):
+            g = p.grad
+            if (g is None or g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape
+                    or not g.is_contiguous()):
+                p.grad = g = buf
+            out.append(g)
+        return out
+
+    def backward(self, state, action, y):
+        """Overwrites every critic parameter's .grad with the gradient of the loss on [B, 10] states, [B, 2] actions
+        (any row stride) and targets y ([B] or [B, 1], any stride); returns the loss of each tower as 0-d device tensors
+        (l1, l2), or the one loss of a DDPG critic."""
+        dev = self.device
+        rows, s_stride = _rows2(state, self.critic.obs_dim, dev, "state")
+        arows, a_stride = _rows2(action, self.critic.act_dim, dev, "action")
+        if arows != rows:
+            raise ValueError(f"uavx: state and action rows differ ({rows} vs {arows})")
+        y_stride = _column(y, rows, dev, "y")
+        if rows < 1 or rows > _actor_lib.GRAD_MAX_ROWS:
+            raise ValueError(f"uavx: FusedCriticLoss takes 1..{_actor_lib.GRAD_MAX_ROWS} rows, got {rows}")
+        for p in self._params:
+            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+                raise TypeError("uavx: FusedCriticLoss reads contiguous float32 parameters on the critic's device")
+        need = self.workspace_bytes(rows)
+        if self._ws.numel() < need:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError(f"uavx: the workspace for {rows} rows must exist before a graph capture: call "
+                                   f"reserve({rows}) first")
+            self.reserve(rows)
+        grads = self._grads()
+        for i, (p, g) in enumerate(zip(self._params, grads)):
+            self._pptrs[i] = p.data_ptr()
+            self._gptrs[i] = g.data_ptr()
+        rc = self._lib.uavx_critic_grad(self.critic._h, _LOSSES[self.loss], self._pptrs, state.data_ptr(), rows, s_stride,
+                                        action.data_ptr(), a_stride, y.data_ptr(), y_stride, self._gptrs,
+                                        self._loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream(dev))
+        _actor_lib.check_critic(rc, "uavx_critic_grad")
+        return (self._loss[0], self._loss[1]) if self.critic.towers == 2 else self._loss[0]
+
+    def close(self):
+        if self._owned is not None:
+            self._owned.close()
+            self._owned = None
