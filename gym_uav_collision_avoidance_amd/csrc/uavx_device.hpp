@@ -124,7 +124,9 @@ __device__ __forceinline__ float wrap_unit(float x) {
 // atan2f for finite inputs, |error| < 7e-7 rad: t = min(|x|,|y|) / max(|x|,|y|) in [0, 1] and one odd minimax polynomial
 // t * P(t^2) of degree 11 over the whole interval (fitted to atan on [0, 1]; 3.4e-7 there, 3.9e-7 evaluated in float32),
 // then the quadrant.  No octant fold: the fold t -> (t-1)/(t+1) past tan(pi/8) cost eight instructions (compare, two selects,
-// sub, add, the pi/4 add and select) against two more polynomial terms.  atan2(0, 0) = 0: mx = 0 gives t = 0 / FLT_MIN.
+// sub, add, the pi/4 add and select) against two more polynomial terms.  atan2(+-0, +0) = +-0: mx = 0 gives t = 0 / FLT_MIN.
+// The quadrant is picked by the SIGN BIT of x, as atan2 does: atan2(+-0, -0) = +-pi (a compare x < 0 took -0 for +0 and gave
+// 0 there, half a turn off math.atan2 for a poked -0.0 velocity or target offset).
 // (Results only feed float32 observation/reward features that are compared at 1e-5.)
 __device__ __forceinline__ float atan2_fast(float y, float x) {
     const float ax = fabsf(x), ay = fabsf(y);
@@ -138,7 +140,7 @@ __device__ __forceinline__ float atan2_fast(float y, float x) {
     pl = fmaf(pl, z, -3.33253950e-1f);
     float r = fmaf(pl * z, t, t);
     r = (ay > ax) ? 1.57079632679489661923f - r : r;
-    r = (x < 0.f) ? kPi - r : r;
+    r = (__float_as_int(x) < 0) ? kPi - r : r;
     return copysignf(r, y);
 }
 

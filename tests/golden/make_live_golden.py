@@ -124,8 +124,44 @@ def make_f64(MUW):
              dict(kind="live_f64", n=n, circular=circular, T=F64_T))
 
 
+# signed zeros: velocities / target offsets / neighbour offsets of (+-0, +-0) poked into a 4-agent world
+SZ_CASES = [(-0.0, 0.0), (-0.0, -0.0), (0.0, -0.0), (0.0, 0.0)]
+
+
+def signed_zero_state(k):
+    """Scenario k of make_signed_zero: float32 locations and targets, float64 velocities, done flags (agent 3 is done when
+    k is odd and agent 2 then sits at (-0, -0), on top of agent 0)."""
+    z, m = 0.0, -0.0
+    loc = np.array([[z, z], [6.0, 1.0], [-5.0, 7.0], [2.0, z]], np.float32)
+    vx, vy = SZ_CASES[k % 4]
+    tx, ty = SZ_CASES[(k // 4) % 4]
+    vel = np.array([[vx, vy], [1.0, 2.0], [vx, vy], list(SZ_CASES[(k + 1) % 4])], np.float64)
+    tgt = np.array([[tx, ty], [20.0, 20.0], [-20.0, 9.0], [30.0, -30.0]], np.float32)
+    done = np.array([0, 0, 0, k % 2], np.uint8)
+    if k % 2:
+        loc[2] = [m, m]
+    return loc, vel, tgt, done
+
+
+def make_signed_zero(MUW):
+    rows = {}
+    for k in range(16):
+        np.random.seed(400 + k)
+        env = MUW(num_agents=4)
+        env.reset()
+        loc, vel, tgt, done = signed_zero_state(k)
+        for i, a in enumerate(env.agent_list):
+            a.location, a.velocity, a.target_location, a.done = loc[i].copy(), vel[i].copy(), tgt[i].copy(), bool(done[i])
+        record(rows, obs=np.array([env._get_obs(a) for a in env.agent_list], np.float64))
+    save("live_signed_zero", rows, dict(kind="live_signed_zero", cases=16))
+
+
 if __name__ == "__main__":
     MUW, UW, _ = ref_loader.load()
+    if sys.argv[1:] == ["signed_zero"]:
+        make_signed_zero(MUW)
+        sys.exit(0)
     make_muw(MUW)
     make_uw(UW)
     make_f64(MUW)
+    make_signed_zero(MUW)

@@ -10,7 +10,7 @@ import pytest
 
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
 from golden_util import load_fixture, tie_agents  # noqa: E402
-from make_live_golden import F64_CASES, MUW_CASES, UW_SEEDS, muw_kwargs  # noqa: E402
+from make_live_golden import F64_CASES, MUW_CASES, UW_SEEDS, muw_kwargs, signed_zero_state  # noqa: E402
 
 
 def _check_multi_step(orc, ref, t, o_obs, o_rew, o_done, ctx, exact_rew=True):
@@ -92,3 +92,16 @@ def test_oracle_float64_episodes_equal_live_reference(oracle_mod, n, circular):
         got[ties, 4:] = 0; want[ties, 4:] = 0
         np.testing.assert_array_equal(got, want, err_msg=ctx)
     assert int(orc.counters[0, 1]) > 0, "nobody reached a target: scenario too short"
+
+
+def test_oracle_signed_zero_angles_equal_live_reference(oracle_mod):
+    """Velocities, target offsets and neighbour offsets of (+-0, +-0), a done agent among them: the oracle's observation
+    equals the reference's recorded one bit for bit, so it follows math.atan2 on signed zeros (atan2(+0, -0) = pi,
+    atan2(-0, -0) = -pi) and can judge the device kernels there."""
+    ref, meta = load_fixture("live_signed_zero")
+    assert ref["obs"][0, 0, 1] == 1.0 and ref["obs"][1, 0, 1] == -1.0
+    for k in range(meta["cases"]):
+        loc, vel, tgt, done = signed_zero_state(k)
+        orc = oracle_mod.OracleMulti(num_envs=1, num_agents=4)
+        orc.set_state(loc=loc, vel=vel, tgt=tgt, flags=done)
+        np.testing.assert_array_equal(orc.observe()[0], ref["obs"][k], err_msg=f"case {k}")
