@@ -1,5 +1,5 @@
-"""ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h), the fused
-actor-inference, critic, TD-target and critic-gradient kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+"""ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h,
+include/uavx_optim.h), the fused actor-inference, critic, TD-target, critic-gradient and optimiser-step kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
 that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
 missing library or device raises."""
 import ctypes
@@ -13,6 +13,7 @@ CSRC = os.path.join(_HERE, "actor_csrc")
 HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_actor.h")
 CRITIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic.h")
 GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic_grad.h")
+OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_optim.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -34,6 +35,10 @@ GRAD_SYMBOLS = ("uavx_critic_grad_version", "uavx_critic_grad_workspace_bytes", 
 GRAD_ABI_VERSION = 1
 GRAD_MSE, GRAD_L1 = 0, 1
 GRAD_MAX_ROWS = 262144  # UAVX_CRITIC_GRAD_MAX_ROWS
+# every symbol include/uavx_optim.h declares
+OPTIM_SYMBOLS = ("uavx_optim_version", "uavx_optim_adam", "uavx_optim_soft_update")
+OPTIM_ABI_VERSION = 1
+OPTIM_MAX_TENSORS = 16  # UAVX_OPTIM_MAX_TENSORS
 
 _lib_handle = None
 
@@ -41,12 +46,12 @@ _lib_handle = None
 def _sources():
     import glob
     return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-            + [HEADER, CRITIC_HEADER, GRAD_HEADER])
+            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER])
 
 
 def source_hash():
     """sha256 over the code (comments and whitespace dropped, _lib._code_only) of actor_csrc/*.hip, *.hpp,
-    include/uavx_actor.h, include/uavx_critic.h and include/uavx_critic_grad.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS
+    include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h and include/uavx_optim.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS
     override; 16 hex digits."""
     import hashlib
     h = hashlib.sha256()
@@ -134,6 +139,13 @@ def load():
     L.uavx_critic_grad_workspace_bytes.argtypes = [vp, i64, ctypes.POINTER(i64)]
     L.uavx_critic_grad.argtypes = [vp, i32, ctypes.POINTER(vp), vp, i64, i64, vp, i64, vp, i64, ctypes.POINTER(vp), vp, vp,
                                    i64, vp]
+    L.uavx_optim_version.restype = i32
+    if L.uavx_optim_version() != OPTIM_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks optimiser ABI version {L.uavx_optim_version()}, this package binds "
+                           f"{OPTIM_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    f64, pvp, pi64 = ctypes.c_double, ctypes.POINTER(vp), ctypes.POINTER(i64)
+    L.uavx_optim_adam.argtypes = [i32, pvp, pvp, pvp, pvp, pvp, pvp, pi64, f64, f64, f64, f64, f64, vp, vp, vp]
+    L.uavx_optim_soft_update.argtypes = [i32, pvp, pvp, pi64, f64, vp]
     _lib_handle = L
     return L
 
