@@ -687,7 +687,7 @@ def test_errors_are_loud(amd):
     env.close()
 
 
-@pytest.mark.parametrize("n", [3, 4, 5, 6, 8, 13, 24])
+@pytest.mark.parametrize("n", [3, 4, 5, 6, 7, 8, 10, 13, 24, 64])
 def test_neighbour_order_on_near_ties(amd, oracle_mod, n):
     """The N>5 scan orders neighbours by an integer key (squared-distance bits truncated to 2^-17 relative, index
     in the low bits), the N = 4 one-step scan by squared distance (scan_neighbours_sq), and both must fall back to the exact (float32 distance, index) order whenever that truncation
