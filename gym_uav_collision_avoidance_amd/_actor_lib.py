@@ -4,9 +4,8 @@ that the environment library and the source hash its profiles carry do not chang
 missing library or device raises."""
 import ctypes
 import os
-import subprocess
 
-from . import _lib
+from . import _native
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "actor_csrc")
@@ -50,56 +49,19 @@ def _sources():
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped, _lib._code_only) of actor_csrc/*.hip, *.hpp,
-    include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h and include/uavx_optim.h, plus the Makefile without comments and any HIPCC / ARCH / HIPFLAGS
-    override; 16 hex digits."""
-    import hashlib
-    h = hashlib.sha256()
-    for f in _sources():
-        h.update(os.path.basename(f).encode())
-        h.update(_lib._code_only(open(f, "r", encoding="utf-8", errors="replace").read()).encode())
-    mk = open(os.path.join(CSRC, "Makefile"), "r", encoding="utf-8", errors="replace").read()
-    mk = "\n".join(l.split("#", 1)[0].rstrip() for l in mk.splitlines() if l.split("#", 1)[0].strip())
-    env = ";".join(f"{k}={os.environ[k]}" for k in ("HIPCC", "ARCH", "HIPFLAGS") if k in os.environ)
-    h.update(b"Makefile")
-    h.update((mk + "\n" + env).encode())
-    return h.hexdigest()[:16]
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the four headers of include/, plus
+    the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
+    return _native.source_hash(CSRC, _sources())
 
 
 def build(force=False):
-    """hipcc build of actor_csrc/ into libuavx_actor.so (gfx950; cross-compiles without a GPU), under an exclusive file
-    lock into a temporary name renamed into place, as _lib.build does."""
-    import fcntl
-    with open(os.path.join(CSRC, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and os.path.exists(LIB_PATH) and _up_to_date():
-                return LIB_PATH
-            tmp = f"libuavx_actor.so.tmp{os.getpid()}"
-            proc = subprocess.run(["make", "-C", CSRC, "-B", f"OUT={tmp}", f"SRCHASH={source_hash()}"], stdout=subprocess.PIPE,
-                                  stderr=subprocess.STDOUT, text=True)
-            if proc.returncode != 0:
-                try:
-                    os.unlink(os.path.join(CSRC, tmp))
-                except OSError:
-                    pass
-                raise RuntimeError(f"uavx: building {LIB_PATH} failed (make exit {proc.returncode}):\n{proc.stdout[-4000:]}")
-            os.replace(os.path.join(CSRC, tmp), LIB_PATH)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB_PATH
+    """hipcc build of actor_csrc/ into libuavx_actor.so (gfx950), under a file lock and renamed into place (_native.build)."""
+    return _native.build(CSRC, LIB_PATH, source_hash, _up_to_date, force)
 
 
 def _up_to_date():
     """Does LIB_PATH carry the hash of the sources in the tree (read from the file, not through dlopen)?"""
-    import re
-    with open(LIB_PATH, "rb") as f:
-        mark = re.search(rb"UAVX_ACTOR_SRC_HASH=([0-9a-f]*)\0", f.read())
-    if mark is None:
-        return False
-    if mark.group(1):
-        return mark.group(1).decode() == source_hash()
-    return os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in _sources() + [os.path.join(CSRC, "Makefile")])
+    return _native.up_to_date(CSRC, LIB_PATH, b"UAVX_ACTOR_SRC_HASH", _sources(), source_hash)
 
 
 def load():

@@ -2,7 +2,8 @@
 missing or no MI355X is visible, every entry point raises."""
 import ctypes
 import os
-import subprocess
+
+from . import _native
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
@@ -103,56 +104,18 @@ class UWStepArgs(ctypes.Structure):  # uavx_uw_step_args
 _lib = None
 
 
-def _code_only(text):
-    """C / C++ source without comments and with every whitespace run outside a literal reduced to one blank: what the compiler
-    sees, near enough.  String and character literals are kept byte for byte (a `//` inside one is not a comment), and a
-    preprocessor directive keeps its line to itself (where a `#define` ends is code)."""
-    import re
-    NL, SP, TB = "\x00", "\x01", "\x02"
-    out, code, i, n = [], [], 0, len(text)
+_code_only = _native.code_only
 
-    def flush():                                          # the code since the last literal (line ends still marked)
-        if code:
-            out.append("".join(code))
-            code.clear()
-    while i < n:
-        c = text[i]
-        if c in "\"'":                                    # literal: copy to the closing quote
-            j = i + 1
-            while j < n and text[j] != c:
-                j += 2 if text[j] == "\\" else 1
-            flush()
-            out.append(text[i:j + 1].replace(" ", SP).replace("\t", TB)); i = j + 1      # blanks of a literal are code
-        elif text.startswith("//", i):
-            while i < n and text[i] != "\n":               # (a line comment ending in a backslash continues: not used here)
-                i += 1
-        elif text.startswith("/*", i):
-            j = text.find("*/", i + 2)
-            i = n if j < 0 else j + 2
-            code.append(" ")
-        else:
-            code.append(NL if c == "\n" else c); i += 1
-    flush()
-    lines, directive = [], False
-    for line in "".join(out).split(NL):
-        body = re.sub(r"[ \t\r\f\v]+", " ", line).strip()
-        if not body:
-            continue
-        starts = body.startswith("#")
-        if starts or directive:                           # a directive (or the continuation of one): its own line
-            lines.append(("\n" if starts else "") + body + ("" if body.endswith("\\") else "\n"))
-            directive = body.endswith("\\")
-        else:
-            lines.append(body + " ")
-    return re.sub(r" +", " ", "".join(lines)).strip().replace(SP, " ").replace(TB, "\t")
+
+def _sources():
+    import glob
+    return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
+            + [os.path.join(os.path.dirname(_HERE), "include", "uavx.h")])
 
 
 def build_flags():
     """What else decides the machine code: the Makefile (comments dropped) and the variables a caller may override it with."""
-    mk = open(os.path.join(CSRC, "Makefile"), "r", encoding="utf-8", errors="replace").read()
-    mk = "\n".join(l.split("#", 1)[0].rstrip() for l in mk.splitlines() if l.split("#", 1)[0].strip())
-    env = ";".join(f"{k}={os.environ[k]}" for k in ("HIPCC", "ARCH", "HIPFLAGS") if k in os.environ)
-    return mk + "\n" + env
+    return _native.build_flags(CSRC)
 
 
 def source_hash():
@@ -162,63 +125,17 @@ def source_hash():
     tuning knobs decide bit-exactness and speed as much as the sources do); first 16 hex digits.  profiles/*_pmc_summary.json
     carry it; bench.py drops a summary whose hash is not the one of the tree; the library embeds it (uavx_build_info) and
     the loader rebuilds on mismatch."""
-    import glob
-    import hashlib
-    h = hashlib.sha256()
-    files = sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-    files.append(os.path.join(os.path.dirname(_HERE), "include", "uavx.h"))
-    for f in files:
-        h.update(os.path.basename(f).encode())
-        h.update(_code_only(open(f, "r", encoding="utf-8", errors="replace").read()).encode())
-    if os.path.exists(os.path.join(CSRC, "Makefile")):
-        h.update(b"Makefile")
-        h.update(build_flags().encode())
-    return h.hexdigest()[:16]
+    return _native.source_hash(CSRC, _sources())
 
 
 def build(force=False):
-    """hipcc build of csrc/ into csrc/libuavx.so (gfx950).  Cross-compiles without a GPU.  Several processes may
-    get here at once (torchrun ranks on a fresh checkout): the build runs under an exclusive file lock into a
-    temporary name and is renamed into place, so nobody ever maps a half-written library."""
-    import fcntl
-    with open(os.path.join(CSRC, ".build.lock"), "w") as lock:
-        fcntl.flock(lock, fcntl.LOCK_EX)
-        try:
-            if not force and os.path.exists(LIB_PATH) and _up_to_date():
-                return LIB_PATH
-            tmp = f"libuavx.so.tmp{os.getpid()}"
-            proc = subprocess.run(["make", "-C", CSRC, "-B", f"OUT={tmp}", f"SRCHASH={source_hash()}"], stdout=subprocess.PIPE,
-                                  stderr=subprocess.STDOUT, text=True)
-            if proc.returncode != 0:
-                try:
-                    os.unlink(os.path.join(CSRC, tmp))
-                except OSError:
-                    pass
-                raise RuntimeError(f"uavx: building {LIB_PATH} failed (make exit {proc.returncode}):\n{proc.stdout[-4000:]}")
-            os.replace(os.path.join(CSRC, tmp), LIB_PATH)
-        finally:
-            fcntl.flock(lock, fcntl.LOCK_UN)
-    return LIB_PATH
+    """hipcc build of csrc/ into csrc/libuavx.so (gfx950), under a file lock and renamed into place (_native.build)."""
+    return _native.build(CSRC, LIB_PATH, source_hash, _up_to_date, force)
 
 
 def _up_to_date():
-    """Is LIB_PATH the build of the sources in the tree?  By content: the library carries the hash of the sources it was
-    built from (uavx_build_info); file times say nothing after a checkout or a snapshot copy.  A library built by a
-    hand-run make (no hash) falls back to comparing file times."""
-    import glob
-    import re
-    # read from the file, not through dlopen: a mapped library stays mapped, and a later CDLL of the rebuilt file under the
-    # same path would hand back the old one
-    with open(LIB_PATH, "rb") as f:
-        mark = re.search(rb"UAVX_SRC_HASH=([0-9a-f]*)\0", f.read())
-    if mark is None:
-        return False          # built before the marker existed
-    built_from = mark.group(1).decode()
-    if built_from:
-        return built_from == source_hash()
-    srcs = glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")) + [
-        os.path.join(os.path.dirname(_HERE), "include", "uavx.h"), os.path.join(CSRC, "Makefile")]
-    return os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(f) for f in srcs)
+    """Is LIB_PATH the build of the sources in the tree (by the hash uavx_build_info carries, _native.up_to_date)?"""
+    return _native.up_to_date(CSRC, LIB_PATH, b"UAVX_SRC_HASH", _sources(), source_hash)
 
 
 def load():

@@ -1,0 +1,342 @@
+// uavx_multi_step.hpp -- one env step of one agent (observation, scripted bodies, step_agent) and the one-step kernel
+// step_kernel.  Included by uavx_multi.hip inside namespace uavx, after uavx_multi_scan.hpp.
+
+// MUW:60-109 in float32 (angles compared on the circle; see DESIGN.md numerics).
+template <class LDS>
+__device__ __forceinline__ void assemble_obs(const MultiParams &p, const WorldLims &w, const LaneMap &m, const LDS &lds,
+                                             const Neigh &nb, float nx, float ny, float speed, float theta, float dist_t,
+                                             float dth, float o[10]) {
+    o[0] = speed * p.inv_vmax_norm;  // MUW:62
+    o[1] = theta * kInvPi;           // MUW:64
+    o[2] = dist_t * w.inv_diag;      // MUW:68
+    o[3] = dth * kInvPi;             // MUW:72
+    // absent neighbour: d=1, bearing (pi + theta) - theta wraps to +-pi -> +-1 (one point on the circle), heading 0
+    const bool has1 = nb.j1 >= 0, has2 = nb.j2 >= 0;
+    const int i1 = m.rbase + (has1 ? nb.j1 : 0), i2 = m.rbase + (has2 ? nb.j2 : 0);
+    const float4 q1 = lds.pos[i1], q2 = lds.pos[i2];
+    const float t1 = lds.theta[i1], t2 = lds.theta[i2];
+    const float b1 = wrap_unit(atan2_fast(q1.w - ny, q1.z - nx) - theta);  // MUW:78-81
+    const float b2 = wrap_unit(atan2_fast(q2.w - ny, q2.z - nx) - theta);  // MUW:88-91
+    const float h1 = wrap_unit(t1 - theta);                                // MUW:82-85
+    const float h2 = wrap_unit(t2 - theta);                                // MUW:92-95
+    o[4] = has1 ? nb.d1 * w.inv_sense : 1.f;                                      // MUW:77
+    o[5] = has1 ? b1 : 1.f;
+    o[6] = has1 ? h1 : 0.f;
+    o[7] = has2 ? nb.d2 * w.inv_sense : 1.f;                                      // MUW:87
+    o[8] = has2 ? b2 : 1.f;
+    o[9] = has2 ? h2 : 0.f;
+}
+
+// Wave-cooperative store of the wave's contiguous obs block (cnt*40 B starting at slot a0): the
+// lane-major [64][10] tile is staged in LDS and written back with lane-contiguous vector stores.
+// Even N: a0 and cnt are even, so the block is 16-byte aligned and a whole number of float4
+// (uavx_create/step check the 16-byte alignment of the caller's obs pointer); otherwise float2.
+template <int NT, class LDS>
+__device__ __forceinline__ void store_obs_block(const MultiParams &p, const LaneMap &m, LDS &lds, const float o[10],
+                                                float *obs_out) {
+    constexpr int T = kWave * LDS::kW;
+    float *stage = lds.obs + m.obs0;
+    if (m.active) {
+        float2 *dst = reinterpret_cast<float2 *>(stage + m.lane * UAVX_OBS_DIM);
+#pragma unroll
+        for (int k = 0; k < 5; k++) dst[k] = make_float2(o[2 * k], o[2 * k + 1]);
+    }
+    group_sync<LDS::kW>();
+    const int nfloat = m.cnt * UAVX_OBS_DIM;
+    const rsrc_t r = make_rsrc(obs_out, (uint32_t)p.E * (uint32_t)p.N * (UAVX_OBS_DIM * 4u));
+    const uint32_t gbase = m.a0 * (UAVX_OBS_DIM * 4u);  // byte offset of the workgroup's block
+    if (NT ? (NT % 2 == 0) : ((p.N & 1) == 0)) {   // uniform: even N => 16-byte aligned block of whole float4
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int f = (k * T + m.lane) * 4;
+            if (f < nfloat) store16_wt(r, gbase + f * 4u, *reinterpret_cast<const float4 *>(stage + f));
+        }
+    } else {
+        // odd N: the block starts 8 bytes off a 16-byte boundary in every second workgroup and ends likewise.  16-byte
+        // stores for the aligned middle, one 8-byte store for a misaligned head / tail (8-byte write-through stores run at
+        // 0.54-0.70x the 16-byte rate: round 1 wrote the whole block that way)
+        const int head = (gbase & 8u) ? 2 : 0;          // uniform over the workgroup
+        const int mid = (nfloat - head) / 4;              // float4 count
+        const int tail = head + mid * 4;                  // first float after the middle (nfloat - tail is 0 or 2)
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int q = k * T + m.lane;
+            if (q < mid) {
+                const float *src = stage + head + q * 4;   // only 8-byte aligned in LDS: two ds_read_b64
+                const float2 lo = *reinterpret_cast<const float2 *>(src), hi = *reinterpret_cast<const float2 *>(src + 2);
+                store16_wt(r, gbase + (uint32_t)(head + q * 4) * 4u, make_float4(lo.x, lo.y, hi.x, hi.y));
+            }
+        }
+        if (m.lane == 0 && head) store8_wt(r, gbase, *reinterpret_cast<const float2 *>(stage));
+        if (m.lane == 1 && tail < nfloat) store8_wt(r, gbase + (uint32_t)tail * 4u, *reinterpret_cast<const float2 *>(stage + tail));
+    }
+    group_sync<LDS::kW>();
+}
+
+// configs[4] extension: a body starts a leg at (x, y) towards waypoint (wx, wy) -- include/uavx.h, uavx_set_body_rule; float32,
+// no FMA, IEEE division and square root, restated bit for bit by the oracle (body_leg).  Off the per-step path (reset, and one
+// env step in `period`).
+__device__ __forceinline__ float4 make_leg(float body_step, float x, float y, float wx, float wy) {
+    const float dx = wx - x, dy = wy - y;
+    const float d = norm32(dx, dy);
+    float4 leg = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (d > 0.f) {
+        const float sc = body_step / d;
+        leg.x = dx * sc; leg.y = dy * sc;
+        leg.w = floorf(d / body_step);   // body_step == 0 (static obstacle): +inf legs of zero displacement
+    }
+    leg.z = atan2_exact(dy, dx);
+    return leg;
+}
+
+// configs[4] extension: the scripted bodies of this lane's env.  Body b is handled by the env's learner lane b % L in trip
+// b / L: position (8 B) and leg record (16 B) loaded, moved when MOVE -- the bodies move BEFORE the learners of the env's
+// sequential loop, so the collision tests and the observations of this step both see the new positions --, staged into its
+// neighbour row {x, y, x, y} + heading, position stored back (8 B) if it moved.  A body that does not take part (b >= the
+// level's b_active) is staged at +inf.
+//   ready   the env was re-initialised by this call: its bodies' rows were staged by the reset path, they do not move.
+template <bool MOVE, class LDS, bool LATEW = false>
+__device__ __forceinline__ void stage_bodies(const MultiParams &p, const LaneMap &m, LDS &lds, uint32_t flags, bool ready,
+                                             uint32_t steps, uint32_t ep_draw) {
+    const int L = p.N;
+    const bool leveled = p.n_levels > 0;
+    const LevelParams *lv = &p.levels[(flags & kLevelMask) >> kLevelShift];   // read only when a curriculum is installed
+    const int b_active = m.active ? (leveled ? lv->b_active : p.B) : 0;
+    const uint32_t kk = steps & (uint32_t)p.body_pmask;     // steps of the current leg that lie behind the body
+    const bool retarget = MOVE && steps != 0u && kk == 0u;  // a new waypoint every `period` steps
+    const float kf = (float)kk;
+#pragma unroll 1
+    for (int k = 0; k < p.kb; k++) {
+        const int b = k * L + m.i;
+        const bool valid = m.active && b < p.B && !ready;
+        const bool on = valid && b < b_active;
+        const uint32_t gi = m.e * (uint32_t)p.B + (uint32_t)b;
+        float2 q = make_float2(INFINITY, INFINITY);
+        float4 leg = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (on) { q = p.body_pos[gi]; leg = p.body_leg[gi]; }
+        if (on && retarget) {
+            // (once per `period` steps: LATEW fetches what this needs from the kernel arguments here, not at the top)
+            const ResetCandidates c = reset_candidates((uint64_t)LATE(LATEW, p, env_offset) + m.e, (uint32_t)(L + b),
+                                                       0x80000000u | (steps >> p.body_pshift), ep_draw, LATE(LATEW, p, body_k0),
+                                                       LATE(LATEW, p, body_k1), leveled ? lv->lox : LATE(LATEW, p, lox),
+                                                       leveled ? lv->loy : LATE(LATEW, p, loy), leveled ? lv->hix : LATE(LATEW, p, hix),
+                                                       leveled ? lv->hiy : LATE(LATEW, p, hiy));
+            leg = make_leg(p.body_step, q.x, q.y, c.sx, c.sy);
+            p.body_leg[gi] = leg;
+        }
+        if (MOVE && on && kf < leg.w) {
+            q.x = q.x + leg.x; q.y = q.y + leg.y;
+            p.body_pos[gi] = q;
+        }
+        if (valid) {
+            lds.pos[m.rbase + L + b] = make_float4(q.x, q.y, q.x, q.y);
+            lds.theta[m.rbase + L + b] = leg.z;
+        }
+    }
+}
+
+// One env step for this lane's agent (state in registers).  MUW:177-241.
+//   frozen: the env was re-initialised by this call (auto-reset); the agent only observes.
+//   EXT: env_steps / ep_draw = the env's step count before this step and the episode index its reset drew with
+//        (scripted bodies); frozen envs had their bodies' rows staged by the reset path.
+template <int NT, bool EXT, class LDS, bool LATEW = false, bool SQ = false>   // SQ: see scan_neighbours
+__device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &m, LDS &lds, AgentRegs &s, double ax,
+                                           double ay, int evaluate, float o[10], float &rew, uint32_t &done_out,
+                                           uint32_t &reach_ev, uint32_t &coll_ev, bool frozen = false,
+                                           uint32_t env_steps = 0, uint32_t ep_draw = 0) {
+    const float sq_sense = sense_limit<EXT>(p, s.flags);
+    const bool was_done = (s.flags & UAVX_FLAG_DONE) != 0;
+    const bool parked = EXT && (s.flags & kFlagInactive) != 0;  // extension: learner switched off by its env's level
+    if (!frozen) s.flags &= ~(kFlagPrevOvr | kFlagJustDone);  // from here on prev_distance is the natural one again
+    const float ox = s.x, oy = s.y;
+    float pd = 0.f, d = 0.f;  // AG:24-25: a done agent returns (0, 0) and does not move
+    if (!was_done && !frozen && !parked) {
+        axis_update(ax, p.tau, p.rtau, p.recip_ok != 0, p.amax, p.vmax, s.vx, s.x);  // AG:26-29
+        axis_update(ay, p.tau, p.rtau, p.recip_ok != 0, p.amax, p.vmax, s.vy, s.y);
+        pd = s.prev_d;                                       // AG:32
+    }
+    const float tdx = s.tx - s.x, tdy = s.ty - s.y;
+    const float dist_t = norm32(tdx, tdy);                   // AG:33 / MUW:67
+    if (!was_done) d = dist_t;
+    // heading; finish() only rescales the velocity (AG:40), so one atan2 serves reward and obs
+    const float theta = atan2_fast((float)s.vy, (float)s.vx);   // MUW:63,185
+    const float dth = wrap_pi(atan2_fast(tdy, tdx) - theta);    // MUW:184-186 == MUW:69-71
+
+    if (m.active) {
+        lds.pos[m.rbase + m.i] = make_float4(ox, oy, s.x, s.y);   // a parked learner sits at +inf
+        lds.theta[m.rbase + m.i] = theta;
+    }
+    if (EXT && p.B > 0) stage_bodies<true, LDS, LATEW>(p, m, lds, s.flags, frozen, env_steps, ep_draw);
+    group_sync<LDS::kW>();
+    const Neigh nb = scan_neighbours<NT, true, LDS, SQ>(sq_sense, m, lds, s.x, s.y);
+    const WorldLims w = world_lims<EXT>(p, s.flags);
+
+    // reward shaping, MUW:188-195 (float32, reciprocals instead of divisions; |error| << 1e-5)
+    const float inv_init = __builtin_amdgcn_rcpf(s.init_d);
+    float r = -0.01f * fminf(p.vmax_norm * inv_init, 1.0f);  // MUW:189
+    r += (50.0f * p.inv_vmax_norm) * (pd - d);               // MUW:190 (pd - d is a float32 subtraction there too)
+    const float frac = d * inv_init * (1.0f / 1.5f);         // MUW:192,194
+    r *= (r > 0.f) ? (1.0f - frac) : (1.0f + frac);
+    r -= 0.01f * fabsf(dth);                                 // MUW:195
+
+    // collisions, MUW:197-210 (exact threshold tests on the squared distance)
+    const bool collision = nb.step_sq_min <= w.sq_two_r;     // MUW:203  dist <= 2R
+    if (collision) r = -2.0f;                                // MUW:204
+    coll_ev = 0;
+    if (nb.step_sq_min <= p.sq_hard && !(s.flags & (UAVX_FLAG_DONE | UAVX_FLAG_COLLIDED)) && !frozen) {  // MUW:207-208
+        coll_ev = 1;                                         // MUW:209
+        s.flags |= UAVX_FLAG_COLLIDED;                       // MUW:210
+    }
+    // termination, MUW:213-227
+    const double sq = fma(s.vy, s.vy, s.vx * s.vx);          // MUW:214 (np.linalg.norm's float64 dot)
+    const bool oob = !(s.x >= w.lo_x && s.x <= w.hi_x && s.y >= w.lo_y && s.y <= w.hi_y);  // MUW:213,224 (exact float32 form)
+    float speed = __builtin_amdgcn_sqrtf((float)sq);         // obs feature only
+    reach_ev = 0;
+    if (frozen) {
+        done_out = 0;
+        r = 0.f;
+    } else if (d < 0.5f && !collision && sq < p.speed_sq_lim) {     // MUW:218
+        done_out = 1;
+        reach_ev = was_done ? 0u : 1u;                       // MUW:220-221
+        s.flags |= UAVX_FLAG_DONE | (was_done ? 0u : kFlagJustDone);  // AG:39
+        const double nv = sqrt(sq);                          // AG:40
+        double fx = s.vx / nv * 0.001, fy = s.vy / nv * 0.001;
+        if (fx != fx || fy != fy) { fx = 0.0; fy = 0.0; }    // AG:41-42
+        s.vx = fx; s.vy = fy;
+        speed = __builtin_amdgcn_sqrtf((float)fma(fy, fy, fx * fx));
+        r += 10.0f;                                          // MUW:223
+    } else if (oob) {
+        done_out = evaluate ? 0u : 1u;                       // MUW:224-225
+    } else {
+        done_out = 0;
+    }
+    if (!frozen) s.prev_d = d;                               // MUW:229
+    rew = r;
+    assemble_obs(p, w, m, lds, nb, s.x, s.y, speed, theta, dist_t, dth, o);  // MUW:233-235
+    if (parked) {  // extension: a parked learner reports an all-zero observation, no reward, done
+#pragma unroll
+        for (int k = 0; k < UAVX_OBS_DIM; k++) o[k] = 0.f;
+        rew = 0.f;
+        done_out = frozen ? 0u : 1u;
+    }
+}
+
+template <bool ACT64>
+__device__ __forceinline__ void load_action(const void *__restrict__ actions, uint32_t a, double &ax, double &ay) {
+    if (ACT64) {
+        const double2 v = reinterpret_cast<const double2 *>(actions)[a];
+        ax = v.x; ay = v.y;
+    } else {
+        const float2 v = reinterpret_cast<const float2 *>(actions)[a];
+        ax = (double)v.x; ay = (double)v.y;
+    }
+}
+
+// One env step per launch (the RL loop's shape: the policy runs between two launches).
+// The arguments the FIRST instructions need -- command pointer, the base of the state allocation and the 32-bit offsets of its
+// arrays, the numbers the lane mapping is made of -- are LEADING SCALAR kernel arguments: gfx950 preloads those into SGPRs before
+// the wavefront starts (Makefile: -mllvm -amdgpu-kernarg-preload-count), so the state loads are the first thing a wavefront does
+// instead of waiting for a scalar load of the argument segment; everything else of the argument struct is fetched behind them
+// (scheduling barrier).  A/B, same library, three runs each (profiles/r04_ab_notes.md section 10): 65 536 x 4 5.76 -> 5.56 us,
+// x 8 10.4 -> 10.0, x 2 4.19 -> 4.09, 32 768 x 4 4.53 -> 4.35.
+// (with bodies the allocator lands on 65 VGPRs = 7 wavefronts per SIMD; asking for 8 gives 62 without a spill)
+#ifndef UAVX_STEPB
+#define UAVX_STEPB 8
+#endif
+// T > 1: T independent one-wavefront tiles per workgroup (own LDS slice, wavefront-level ordering only) -- fewer workgroups for
+// the dispatcher to place.  Pays only where one-wavefront workgroups fill every slot exactly once and live short (65 536 x 8:
+// the 2.3 us over which 8 192 workgroups are placed is a large share of a 6 us wavefront); see tiles_for().
+template <int NT, bool ACT64, bool EXT, int W, int T = 1>
+__global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) void step_kernel(
+    const void *__restrict__ actions, char *slab, uint32_t off_vel, uint32_t off_goal, uint32_t off_rec, uint32_t off_wsteps,
+    uint32_t num_envs, uint32_t n_agents, uint32_t envs_per_group, uint32_t magic, uint32_t nslots, MultiParams p, int evaluate,
+    float *__restrict__ obs_out, float *__restrict__ rew_out, uint8_t *__restrict__ done_out) {
+    static_assert(T == 1 || W == 1, "tiles are one-wavefront workgroups side by side");
+    using LDS = std::conditional_t<(T > 1), LdsTiles<T>, LdsT<EXT, W>>;
+    static_assert(T == 1 || !EXT, "tiles: the plain variants only");
+    __shared__ LDS lds;
+    const uint32_t tile = T > 1 ? (uint32_t)__builtin_amdgcn_readfirstlane((int)(threadIdx.x / kWave)) : 0u;   // (a scalar)
+    // 4 UAVs, one step: state rows through buffer resources (16 scalar registers for the four of them; the other variants have none
+    // to spare) and the squared-distance neighbour scan (scan_neighbours)
+    constexpr bool BUF = NT == 4 && !EXT && T == 1;
+    float2 *const pos_b = reinterpret_cast<float2 *>(slab);
+    double2 *const vel_b = reinterpret_cast<double2 *>(slab + off_vel);
+    Goal *const goal_b = reinterpret_cast<Goal *>(slab + off_goal);
+    const uint32_t nslot = num_envs * n_agents;   // E*N < 2^26 (uavx_create): every byte offset below fits 32 bits
+    const rsrc_t r_act = make_rsrc(actions, nslot * (ACT64 ? 16u : 8u));
+    const rsrc_t r_pos = make_rsrc(slab, nslot * 8u), r_vel = make_rsrc(slab + off_vel, nslot * 16u);
+    const rsrc_t r_goal = make_rsrc(slab + off_goal, nslot * 16u);
+    const uint32_t wave_id = blockIdx.x * T + tile;
+    const LaneMap m = lane_map_from<NT, EXT, W>(num_envs, (int)n_agents, (int)envs_per_group, (int)magic, (int)nslots, wave_id,
+                                                T > 1 ? threadIdx.x % kWave : threadIdx.x, tile);
+    AgentRegs s = {};
+    double ax = 0.0, ay = 0.0;
+    uint4 rec = make_uint4(0, 0, 0, 0);
+    uint32_t wave_count = 0;
+    {
+        // Unconditional (idle lanes of the last workgroup read slot 0 and drop what they compute): the requests leave in front
+        // of every scalar load of the argument struct.  The command goes first: prev_distance is arithmetic on the state, and
+        // a load placed behind that would start a second memory round trip after the first one has come back.
+        const uint32_t el = m.active ? m.e : 0u, al = m.active ? m.a : 0u;
+        if (EXT) {  // the bodies' waypoint schedule runs on the env's step count and episode index
+            rec = reinterpret_cast<const uint4 *>(slab + off_rec)[el];
+            wave_count = reinterpret_cast<const uint32_t *>(slab + off_wsteps)[wave_id];
+        }
+        // BUF: buffer loads, one 32-bit lane offset per row size on top of the scalar bases (a global load needs a 64-bit
+        // address per lane and array)
+        if (!BUF) {
+            load_action<ACT64>(actions, al, ax, ay);
+            const float2 d = pos_b[al];
+            const double2 v = vel_b[al];
+            const Goal g = goal_b[al];
+            __builtin_amdgcn_sched_barrier(0);
+            s.x = d.x; s.y = d.y; s.vx = v.x; s.vy = v.y;
+            s.tx = g.tx; s.ty = g.ty; s.init_d = g.init_d; s.flags = g.flags;
+        } else {
+            if (ACT64) {
+                const u32x4 c = __builtin_amdgcn_raw_buffer_load_b128(r_act, al * 16u, 0, 0);
+                ax = __hiloint2double(c.y, c.x); ay = __hiloint2double(c.w, c.z);
+            } else {
+                const u32x2 c = __builtin_amdgcn_raw_buffer_load_b64(r_act, al * 8u, 0, 0);
+                ax = (double)__uint_as_float(c.x); ay = (double)__uint_as_float(c.y);
+            }
+            const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(r_pos, al * 8u, 0, 0);
+            const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r_vel, al * 16u, 0, 0);
+            const u32x4 g = __builtin_amdgcn_raw_buffer_load_b128(r_goal, al * 16u, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            s.x = __uint_as_float(d.x); s.y = __uint_as_float(d.y);
+            s.vx = __hiloint2double(v.y, v.x); s.vy = __hiloint2double(v.w, v.z);
+            s.tx = __uint_as_float(g.x); s.ty = __uint_as_float(g.y); s.init_d = __uint_as_float(g.z); s.flags = g.w;
+        }
+        s.prev_d = natural_prev_d(s.flags, s.x, s.y, s.tx, s.ty);
+        if (m.active && (s.flags & kFlagPrevOvr)) s.prev_d = p.prev_ovr[m.a];  // rare: only after a caller poked the state
+    }
+    const uint32_t flags_in = s.flags;
+    float o[10], rew;
+    uint32_t dn, re, ce;
+    step_agent<NT, EXT, LDS, false, BUF>(p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, false, wave_count - rec.x,
+                                    ((rec.y & ~kRecEnded) - 1u) & ~kRecEnded);
+    if (m.active) {
+        if (!BUF) {
+            if (!(EXT && (flags_in & kFlagInactive))) store_agent(p, pos_b, vel_b, goal_b, m.a, s, flags_in);
+            rew_out[m.a] = rew;
+            done_out[m.a] = (uint8_t)dn;
+        } else {   // store_agent() through the buffer resources of the loads
+            store16_wt(r_vel, m.a * 16u, make_double2(s.vx, s.vy));
+            const u32x2 d = {__float_as_uint(s.x), __float_as_uint(s.y)};
+            __builtin_amdgcn_raw_buffer_store_b64(d, r_pos, m.a * 8u, 0, 0);
+            if (s.flags != flags_in) __builtin_amdgcn_raw_buffer_store_b32(s.flags, r_goal, m.a * 16u + 12u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), make_rsrc(rew_out, nslot * 4u), m.a * 4u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b8((uint8_t)dn, make_rsrc(done_out, nslot), m.a, 0, 0);
+        }
+        if (re) atomicAdd(&p.reach[m.e], 1u);                // MUW:221
+        if (ce) atomicAdd(&p.coll[m.e], 1u);                 // MUW:209
+        if (!(fabsf(rew) < INFINITY)) atomicAdd(&p.nonfin[m.e], 1u);   // the tripwire of test_ddpg_multi.py:114-130, per env
+        if (m.lane == 0) {
+            uint32_t *const ws = reinterpret_cast<uint32_t *>(slab + off_wsteps);
+            if (EXT) ws[m.wave] = wave_count + 1u;             // single writer: this wave (MUW:238)
+            else atomicAdd(&ws[m.wave], 1u);                   // MUW:238 for every env of this wave (no-return)
+        }
+    }
+    store_obs_block<NT>(p, m, lds, o, obs_out);
+}

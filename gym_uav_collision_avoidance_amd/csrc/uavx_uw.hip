@@ -133,7 +133,7 @@ __device__ __forceinline__ void uw_load_action(const void *__restrict__ actions,
 
 // The pointers the FIRST instructions need and the env count are leading scalar kernel arguments: gfx950 preloads them into SGPRs
 // (Makefile: -mllvm -amdgpu-kernarg-preload-count), so the four loads leave before any scalar load of the argument struct (see
-// step_kernel in uavx_multi.hip).  A/B (profiles/r04_ab_notes.md section 10): 4 096 envs 2.58 -> 2.48 us, 65 536 3.14 -> 3.00,
+// step_kernel in uavx_multi_step.hpp).  A/B (profiles/r04_ab_notes.md section 10): 4 096 envs 2.58 -> 2.48 us, 65 536 3.14 -> 3.00,
 // 1 Mi 17.7 -> 16.7 (0.69 -> 0.73 of the HBM figure).
 // (pos_in / vel_in / goal_in are p.pos / p.vel / p.goal, which the kernel also stores through: not `__restrict__`.  The same
 //  treatment of uw_step_ex_kernel -- record, command and state requested together -- measured no gain: 5.27 vs 5.23 us at 65 536
@@ -310,41 +310,7 @@ struct uavx_uw_handle {
     std::string err;
 };
 
-bool uavx_recip_division_exact(double tau);  // uavx_multi.hip
-float uavx_f32_at_or_above(double b);
-float uavx_f32_at_or_below(double b);
-
-namespace {
-
-int uw_fail(uavx_uw_handle *h, int code, const std::string &msg) {
-    if (h) h->err = msg;
-    return code;
-}
-#define UW_HIP(h, call)                                                                               \
-    do {                                                                                              \
-        hipError_t e_ = (call);                                                                       \
-        if (e_ != hipSuccess) return uw_fail(h, UAVX_ERR_HIP, std::string(#call ": ") + hipGetErrorString(e_)); \
-    } while (0)
-
-struct UwDeviceGuard {
-    int prev = -1, want;
-    hipError_t err = hipSuccess;
-    explicit UwDeviceGuard(int device) : want(device) {
-        err = hipGetDevice(&prev);
-        if (err == hipSuccess && prev != want) err = hipSetDevice(want);
-    }
-    ~UwDeviceGuard() {
-        if (prev >= 0 && prev != want) (void)hipSetDevice(prev);
-    }
-};
-#define UW_ENTER(h)                  \
-    UwDeviceGuard guard_((h)->device); \
-    if (guard_.err != hipSuccess) return uw_fail((h), UAVX_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(guard_.err))
-
-inline size_t uw_align(size_t x) { return (x + 255) / 256 * 256; }
-inline dim3 env_grid(const uavx_uw_handle *h) { return dim3((unsigned)((h->p.E + kBlock - 1) / kBlock)); }
-
-}  // namespace
+#include "uavx_host_util.hpp"
 
 extern "C" {
 
@@ -374,18 +340,18 @@ int uavx_uw_create(const uavx_uw_config *cfg, int64_t num_envs, int64_t env_offs
     p.inv_diag = (float)(1.0 / std::sqrt(std::fma(cfg->y_size, cfg->y_size, cfg->x_size * cfg->x_size)));
     p.E = num_envs;
     p.env_offset = env_offset;
-    UwDeviceGuard guard(device);
+    DeviceGuard guard(device);
     if (guard.err != hipSuccess) { delete h; return UAVX_ERR_HIP; }
     const size_t E = (size_t)num_envs;
     size_t off = 0;
-    const size_t o_pos = off;  off = uw_align(off + E * sizeof(float2));
-    const size_t o_vel = off;  off = uw_align(off + E * sizeof(double2));
-    const size_t o_goal = off; off = uw_align(off + E * sizeof(UwGoal));
-    const size_t o_ovr = off;  off = uw_align(off + E * 4);
-    const size_t o_wsteps = off; off = uw_align(off + ((E + kBlock - 1) / kBlock) * 4);
-    const size_t o_rec = off;   off = uw_align(off + E * sizeof(uint4));
-    const size_t o_finc = off;  off = uw_align(off + E * sizeof(uint4));
-    const size_t o_finr = off;  off = uw_align(off + E * 4);
+    const size_t o_pos = off;  off = align_up(off + E * sizeof(float2), 256);
+    const size_t o_vel = off;  off = align_up(off + E * sizeof(double2), 256);
+    const size_t o_goal = off; off = align_up(off + E * sizeof(UwGoal), 256);
+    const size_t o_ovr = off;  off = align_up(off + E * 4, 256);
+    const size_t o_wsteps = off; off = align_up(off + ((E + kBlock - 1) / kBlock) * 4, 256);
+    const size_t o_rec = off;   off = align_up(off + E * sizeof(uint4), 256);
+    const size_t o_finc = off;  off = align_up(off + E * sizeof(uint4), 256);
+    const size_t o_finr = off;  off = align_up(off + E * 4, 256);
     if (hipMalloc(&h->slab, off) != hipSuccess) { delete h; return UAVX_ERR_ALLOC; }
     if (hipMemset(h->slab, 0, off) != hipSuccess) { (void)hipFree(h->slab); delete h; return UAVX_ERR_HIP; }
     char *b = static_cast<char *>(h->slab);
@@ -404,7 +370,7 @@ int uavx_uw_create(const uavx_uw_config *cfg, int64_t num_envs, int64_t env_offs
 int uavx_uw_destroy(uavx_uw_handle *h) {
     if (!h) return UAVX_ERR_INVALID_ARG;
     if (h->slab) {
-        UwDeviceGuard guard(h->device);
+        DeviceGuard guard(h->device);
         (void)hipFree(h->slab);
     }
     delete h;
@@ -416,116 +382,82 @@ const char *uavx_uw_last_error(const uavx_uw_handle *h) { return h ? h->err.c_st
 int uavx_uw_observe(uavx_uw_handle *h, float *obs, void *stream) {
     if (!h) return UAVX_ERR_INVALID_ARG;
     if (!obs || (reinterpret_cast<uintptr_t>(obs) & 15u))
-        return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_observe: obs is NULL or not 16-byte aligned");
-    UW_ENTER(h);
-    hipLaunchKernelGGL(uw_observe_kernel, env_grid(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->p,
-                       reinterpret_cast<float4 *>(obs));
-    UW_HIP(h, hipGetLastError());
-    return UAVX_OK;
+        return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_observe: obs is NULL or not 16-byte aligned");
+    UAVX_ENTER(h);
+    return launch_items(h, uw_observe_kernel, h->p.E, static_cast<hipStream_t>(stream), h->p, reinterpret_cast<float4 *>(obs));
 }
 
 int uavx_uw_reset(uavx_uw_handle *h, const uint8_t *mask, uint64_t seed, float *obs, void *stream) {
     if (!h) return UAVX_ERR_INVALID_ARG;
     if (obs && (reinterpret_cast<uintptr_t>(obs) & 15u))
-        return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_reset: obs not 16-byte aligned");
-    UW_ENTER(h);
+        return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_reset: obs not 16-byte aligned");
+    UAVX_ENTER(h);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    hipLaunchKernelGGL(uw_reset_kernel, env_grid(h), dim3(kBlock), 0, st, h->p, mask, seed);
-    UW_HIP(h, hipGetLastError());
-    if (obs) {
-        hipLaunchKernelGGL(uw_observe_kernel, env_grid(h), dim3(kBlock), 0, st, h->p, reinterpret_cast<float4 *>(obs));
-        UW_HIP(h, hipGetLastError());
-    }
-    return UAVX_OK;
+    const int rc = launch_items(h, uw_reset_kernel, h->p.E, st, h->p, mask, seed);
+    if (rc != UAVX_OK || !obs) return rc;
+    return launch_items(h, uw_observe_kernel, h->p.E, st, h->p, reinterpret_cast<float4 *>(obs));
 }
 
 int uavx_uw_step(uavx_uw_handle *h, const void *actions, int action_dtype, float *obs, float *rew, uint8_t *done,
                  float *info_distance, void *stream) {
     if (!h) return UAVX_ERR_INVALID_ARG;
-    if (!actions || !obs || !rew || !done) return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step: NULL buffer");
+    if (!actions || !obs || !rew || !done) return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step: NULL buffer");
     if (action_dtype != UAVX_F32 && action_dtype != UAVX_F64)
-        return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step: action_dtype must be UAVX_F32 or UAVX_F64");
+        return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step: action_dtype must be UAVX_F32 or UAVX_F64");
     if ((reinterpret_cast<uintptr_t>(obs) & 15u) || (reinterpret_cast<uintptr_t>(actions) & (action_dtype == UAVX_F64 ? 15u : 7u)) ||
         (reinterpret_cast<uintptr_t>(rew) & 3u) || (reinterpret_cast<uintptr_t>(info_distance) & 3u))
-        return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step: obs must be 16-byte aligned, actions 8 (float32) / 16 (float64), rew and info 4");
-    UW_ENTER(h);
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (action_dtype == UAVX_F64)
-        hipLaunchKernelGGL((uw_step_kernel<true>), env_grid(h), dim3(kBlock), 0, st, actions, h->p.pos, h->p.vel, h->p.goal, (int64_t)h->p.E,
-                           h->p, reinterpret_cast<float4 *>(obs), rew, done, info_distance);
-    else
-        hipLaunchKernelGGL((uw_step_kernel<false>), env_grid(h), dim3(kBlock), 0, st, actions, h->p.pos, h->p.vel, h->p.goal, (int64_t)h->p.E,
-                           h->p, reinterpret_cast<float4 *>(obs), rew, done, info_distance);
-    UW_HIP(h, hipGetLastError());
-    return UAVX_OK;
+        return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step: obs must be 16-byte aligned, actions 8 (float32) / 16 (float64), rew and info 4");
+    UAVX_ENTER(h);
+    const auto kernel = action_dtype == UAVX_F64 ? &uw_step_kernel<true> : &uw_step_kernel<false>;
+    return launch_items(h, kernel, h->p.E, static_cast<hipStream_t>(stream), actions, h->p.pos, h->p.vel, h->p.goal, (int64_t)h->p.E, h->p,
+                        reinterpret_cast<float4 *>(obs), rew, done, info_distance);
 }
 
 int uavx_uw_step_ex(uavx_uw_handle *h, const uavx_uw_step_args *a, void *stream) {
     if (!h || !a) return UAVX_ERR_INVALID_ARG;
-    if (!a->actions || !a->obs || !a->rew || !a->done) return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: NULL buffer");
+    if (!a->actions || !a->obs || !a->rew || !a->done) return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: NULL buffer");
     if (a->action_dtype != UAVX_F32 && a->action_dtype != UAVX_F64)
-        return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: action_dtype must be UAVX_F32 or UAVX_F64");
+        return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: action_dtype must be UAVX_F32 or UAVX_F64");
     if (a->action_mode != UAVX_ACTION_CARTESIAN && a->action_mode != UAVX_ACTION_POLAR &&
         a->action_mode != UAVX_ACTION_POLAR_REFERENCE)
-        return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: unknown action_mode");
+        return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: unknown action_mode");
     if ((reinterpret_cast<uintptr_t>(a->obs) & 15u) || (reinterpret_cast<uintptr_t>(a->actions) & (a->action_dtype == UAVX_F64 ? 15u : 7u)) ||
         (reinterpret_cast<uintptr_t>(a->rew) & 3u) || (reinterpret_cast<uintptr_t>(a->info_distance) & 3u))
-        return uw_fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: obs must be 16-byte aligned, actions 8 (float32) / 16 (float64), rew and info 4");
-    UW_ENTER(h);
+        return fail(h, UAVX_ERR_INVALID_ARG, "uavx_uw_step_ex: obs must be 16-byte aligned, actions 8 (float32) / 16 (float64), rew and info 4");
+    UAVX_ENTER(h);
     UwExtra x;
     x.action_mode = a->action_mode; x.auto_reset = a->auto_reset; x.track_returns = a->track_returns;
     x.step_cap = a->step_cap; x.seed_lo = (uint32_t)a->seed; x.seed_hi = (uint32_t)(a->seed >> 32);
     x.reset_mask = a->reset_mask; x.ended = a->ended; x.truncated = a->truncated;
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    if (a->action_mode == UAVX_ACTION_POLAR_REFERENCE) {
-        if (a->action_dtype == UAVX_F64)
-            hipLaunchKernelGGL((uw_step_ex_ref_kernel<true>), env_grid(h), dim3(kBlock), 0, st, h->p, x, a->actions,
-                               reinterpret_cast<float4 *>(a->obs), a->rew, a->done, a->info_distance);
-        else
-            hipLaunchKernelGGL((uw_step_ex_ref_kernel<false>), env_grid(h), dim3(kBlock), 0, st, h->p, x, a->actions,
-                               reinterpret_cast<float4 *>(a->obs), a->rew, a->done, a->info_distance);
-    } else if (a->action_dtype == UAVX_F64)
-        hipLaunchKernelGGL((uw_step_ex_kernel<true>), env_grid(h), dim3(kBlock), 0, st, h->p, x, a->actions,
-                           reinterpret_cast<float4 *>(a->obs), a->rew, a->done, a->info_distance);
-    else
-        hipLaunchKernelGGL((uw_step_ex_kernel<false>), env_grid(h), dim3(kBlock), 0, st, h->p, x, a->actions,
-                           reinterpret_cast<float4 *>(a->obs), a->rew, a->done, a->info_distance);
-    UW_HIP(h, hipGetLastError());
-    return UAVX_OK;
+    const bool f64 = a->action_dtype == UAVX_F64;
+    const auto kernel = a->action_mode == UAVX_ACTION_POLAR_REFERENCE ? (f64 ? &uw_step_ex_ref_kernel<true> : &uw_step_ex_ref_kernel<false>)
+                                                                      : (f64 ? &uw_step_ex_kernel<true> : &uw_step_ex_kernel<false>);
+    return launch_items(h, kernel, h->p.E, static_cast<hipStream_t>(stream), h->p, x, a->actions, reinterpret_cast<float4 *>(a->obs), a->rew,
+                        a->done, a->info_distance);
 }
 
 int uavx_uw_get_episode_stats(uavx_uw_handle *h, uint32_t *counts, float *returns, void *stream) {
     if (!h) return UAVX_ERR_INVALID_ARG;
-    UW_ENTER(h);
-    hipLaunchKernelGGL(uw_episode_stats_kernel, env_grid(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->p,
-                       counts, returns, 0);
-    UW_HIP(h, hipGetLastError());
-    return UAVX_OK;
+    UAVX_ENTER(h);
+    return launch_items(h, uw_episode_stats_kernel, h->p.E, static_cast<hipStream_t>(stream), h->p, counts, returns, 0);
 }
 
 int uavx_uw_clear_episode_stats(uavx_uw_handle *h, void *stream) {
     if (!h) return UAVX_ERR_INVALID_ARG;
-    UW_ENTER(h);
-    hipLaunchKernelGGL(uw_episode_stats_kernel, env_grid(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->p,
-                       (uint32_t *)nullptr, (float *)nullptr, 1);
-    UW_HIP(h, hipGetLastError());
-    return UAVX_OK;
+    UAVX_ENTER(h);
+    return launch_items(h, uw_episode_stats_kernel, h->p.E, static_cast<hipStream_t>(stream), h->p, (uint32_t *)nullptr, (float *)nullptr, 1);
 }
 
 int uavx_uw_get_state(uavx_uw_handle *h, const uavx_uw_state_view *dst, void *stream) {
     if (!h || !dst) return UAVX_ERR_INVALID_ARG;
-    UW_ENTER(h);
-    hipLaunchKernelGGL(uw_get_state_kernel, env_grid(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->p, *dst);
-    UW_HIP(h, hipGetLastError());
-    return UAVX_OK;
+    UAVX_ENTER(h);
+    return launch_items(h, uw_get_state_kernel, h->p.E, static_cast<hipStream_t>(stream), h->p, *dst);
 }
 
 int uavx_uw_set_state(uavx_uw_handle *h, const uavx_uw_state_view *src, void *stream) {
     if (!h || !src) return UAVX_ERR_INVALID_ARG;
-    UW_ENTER(h);
-    hipLaunchKernelGGL(uw_set_state_kernel, env_grid(h), dim3(kBlock), 0, static_cast<hipStream_t>(stream), h->p, *src);
-    UW_HIP(h, hipGetLastError());
-    return UAVX_OK;
+    UAVX_ENTER(h);
+    return launch_items(h, uw_set_state_kernel, h->p.E, static_cast<hipStream_t>(stream), h->p, *src);
 }
 
 }  // extern "C"

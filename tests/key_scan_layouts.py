@@ -1,4 +1,4 @@
-"""Crafted neighbour layouts for the 6-64 UAV neighbour key scan (scan_neighbours of csrc/uavx_multi.hip, N > 5 and the
+"""Crafted neighbour layouts for the 6-64 UAV neighbour key scan (scan_neighbours of csrc/uavx_multi_scan.hpp, N > 5 and the
 8-UAV specialisation), and a host model of its integer key arithmetic (numpy only).
 
 The device arithmetic (float32, no FMA: neighbour_layouts.squares) is restated as it is written in the kernel:
@@ -43,7 +43,7 @@ SENSE = (9.0, 15.0, 7.3, 6.1)   # bits(sq_limit_lt(d)) & 63 = 63, 0, 54, 10: the
 WORLD = dict(x_size=600.0, y_size=600.0)
 EXT_SLOTS = 192                 # kExtSlots: neighbour rows of one wavefront of the kernels with scripted bodies
 
-# pick_group_waves() of csrc/uavx_multi.hip: its table, copied as data (agent counts outside it are not used here)
+# pick_group_waves() of csrc/uavx_multi_launch.hpp: its table, copied as data (agent counts outside it are not used here)
 GROUP_WAVES = {1: 1, 2: 1, 4: 1, 5: 1, 8: 1, 3: 3, 6: 3, 7: 3, 11: 3, 12: 3, 24: 3, 48: 3, 9: 2, 10: 2, 15: 2, 20: 2, 40: 2,
                13: 1, 14: 1, 16: 1, 28: 1, 32: 1, 64: 1}
 

@@ -2,7 +2,7 @@
 
 The library is built with -ffp-contract=off, so numpy float32 reproduces the device's neighbour arithmetic exactly:
   dx = f32(xj - xi), s = f32(f32(dx*dx) + f32(dy*dy)); in range iff s < sq_sense, where sq_sense is the smallest float32 s
-  with sqrtf(s) >= f32(d_sense) (sq_limit_lt in uavx_multi.hip); the distance is the correctly rounded sqrtf(s); the two
+  with sqrtf(s) >= f32(d_sense) (sq_limit_lt in uavx_multi_handle.hpp); the distance is the correctly rounded sqrtf(s); the two
   nearest are ordered by (distance, index).
 The squared-distance scan of the one-step kernel at N = 4 (scan_neighbours_sq) keeps the three smallest in-range squares
 s1 <= s2 <= s3 and sends its whole wavefront through the exact scan when any active lane has s3 < inf and

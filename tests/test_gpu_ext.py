@@ -153,7 +153,7 @@ def test_staging_overlaps_the_reset_it_serves(amd, oracle_mod, monkeypatch, cap,
     half (or a third) of the envs from the parked layouts while staging workgroups of the same launch scan, and redraw, the
     layouts of those very envs -- from in front of the env-workgroups and from behind them (the library picks by launch shape;
     UAVX_STAGE_BEHIND, read when the handle is made, forces either).  What keeps that correct is written down at stage_ahead
-    (csrc/uavx_multi.hip): the slot a re-initialising env reads is left alone while its "ended" mark stands, and the mark is
+    (csrc/uavx_multi_reset.hpp): the slot a re-initialising env reads is left alone while its "ended" mark stands, and the mark is
     cleared by the env's last store, after every load from the staging arrays has returned.  Every output and the whole state
     against the oracle, every step; a seed change in the middle invalidates everything that is parked."""
     import torch

@@ -374,6 +374,73 @@ def test_tile_pairs_equal_one_wavefront_workgroups(amd, monkeypatch, E):
     a.close(); b.close()
 
 
+@pytest.mark.parametrize("call", ["step", "step_ex", "step_k"])
+@pytest.mark.parametrize("E,n,tiles", [(17, 8, None), (13, 8, "2"), (16, 8, "2"), (33, 4, None)])
+def test_float64_commands_on_every_step_launch_vs_oracle(amd, oracle_mod, monkeypatch, E, n, tiles, call):
+    """float64 velocity commands through each step launch -- uavx_step, uavx_step_ex, uavx_step_k -- on two full
+    env-workgroups plus a partial one (17 envs of 8 UAVs, 33 of 4) and on pairs of one-wavefront tiles whose last tile is
+    partial (13 envs) or full (16): state bit for bit against the oracle after every step, observations and rewards to 1e-5."""
+    if tiles:
+        monkeypatch.setenv("UAVX_TILES", tiles)
+    kw = dict(x_size=26.0, y_size=26.0, num_agents=n, d_sense=9.0)
+    env = amd.BatchedMultiUAVWorld2D(E, seed=77, env_offset=5, **kw)
+    orc = oracle_mod.OracleMulti(num_envs=E, nthreads=2, **kw)
+    env.reset()
+    orc.reset_philox(77, env_offset=5)
+    rng = np.random.default_rng(E)
+    T = 3
+    acts = []
+    for t in range(T):      # goal-seeking commands, float64 (the tape of step_k is drawn up front: open loop)
+        acts.append((orc.tgt - orc.loc) * rng.uniform(0.2, 3.0, size=(E, n, 1)) + rng.normal(0, 0.5 + t, size=(E, n, 2)))
+        assert acts[-1].dtype == np.float64
+    if call == "step_k":
+        tape_out = env.step_k(np.stack(acts), tape_out=True)
+    for t in range(T):
+        ctx = f"{call} E={E} n={n} tiles={tiles} step {t}"
+        if call == "step_ex":
+            obs_g, rew_g, done_g, info = env.step_ex(acts[t], auto_reset="agent0_done", step_cap=2, track_returns=True)
+            obs_o, rew_o, done_o, rmask_o = orc.step_ex(acts[t], reset_policy=1, step_cap=2, track_returns=True, seed=77, env_offset=5)
+            np.testing.assert_array_equal(_np(info["reset_mask"]).astype(np.uint8), rmask_o, err_msg=ctx)
+        else:
+            obs_g, rew_g, done_g = env.step(acts[t])[:3] if call == "step" else [x[t] for x in tape_out[:3]]
+            obs_o, rew_o, done_o = orc.step(acts[t], env_offset=5)
+        np.testing.assert_array_equal(_np(done_g).astype(np.uint8), done_o, err_msg=ctx)
+        assert obs_err(_np(obs_g), obs_o) <= TOL and float(np.abs(_np(rew_g) - rew_o).max()) <= TOL, ctx
+        if call != "step_k" or t == T - 1:
+            st, ref = env.get_state(), orc.get_state()
+            for key in ("loc", "vel", "tgt", "init_d", "prev_d", "flags"):
+                np.testing.assert_array_equal(_np(st[key]), ref[key], err_msg=f"{ctx} {key}")
+            np.testing.assert_array_equal(_np(st["counters"]), ref["counters"].astype(np.int32), err_msg=ctx)
+    env.close()
+
+
+@pytest.mark.parametrize("E", [13, 16])
+def test_float64_polar_commands_on_tile_pairs(amd, monkeypatch, E):
+    """float64 actions through uavx_step_ex's polar and polar-reference launches on pairs of one-wavefront tiles (8 UAVs;
+    last tile partial / full): bit for bit what one-wavefront workgroups give, as test_tile_pairs_equal_one_wavefront_workgroups
+    checks for float32 actions."""
+    import torch
+    n = 8
+    monkeypatch.setenv("UAVX_TILES", "2")
+    a = amd.BatchedMultiUAVWorld2D(E, num_agents=n, seed=9)
+    monkeypatch.setenv("UAVX_TILES", "1")
+    b = amd.BatchedMultiUAVWorld2D(E, num_agents=n, seed=9)
+    a.reset(); b.reset()
+    g = torch.Generator(device="cpu").manual_seed(2)
+    for t in range(4):
+        act = (torch.rand((E, n, 2), generator=g, dtype=torch.float64) * 2 - 1).to(a.device)
+        polar = "reference" if t % 2 else True
+        ra = a.step_ex(act, polar=polar, auto_reset="agent0_done", step_cap=3, track_returns=True)
+        rb = b.step_ex(act, polar=polar, auto_reset="agent0_done", step_cap=3, track_returns=True)
+        for x, y in zip(ra[:3], rb[:3]):
+            assert torch.equal(x, y), (t, polar)
+        assert torch.equal(ra[3]["reset_mask"], rb[3]["reset_mask"]), t
+    sa, sb = a.get_state(), b.get_state()
+    for k in sa:
+        assert torch.equal(sa[k], sb[k]), k
+    a.close(); b.close()
+
+
 @pytest.mark.parametrize("n", [3, 10, 12])
 def test_workgroup_width_does_not_change_results(amd, monkeypatch, n):
     """The runtime-N kernels pick their wavefronts per workgroup from a measured table (three at 3 and 12 UAVs, two at 10);
