@@ -1,5 +1,6 @@
 """ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h,
-include/uavx_optim.h), the fused actor-inference, critic, TD-target, critic-gradient and optimiser-step kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+include/uavx_optim.h, include/uavx_replay.h), the fused actor-inference, critic, TD-target, critic-gradient, optimiser-step
+and replay-sampling kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
 that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
 missing library or device raises."""
 import ctypes
@@ -13,6 +14,7 @@ HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_actor.h")
 CRITIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic.h")
 GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic_grad.h")
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_optim.h")
+REPLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_replay.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -38,18 +40,29 @@ GRAD_MAX_ROWS = 262144  # UAVX_CRITIC_GRAD_MAX_ROWS
 OPTIM_SYMBOLS = ("uavx_optim_version", "uavx_optim_adam", "uavx_optim_soft_update")
 OPTIM_ABI_VERSION = 1
 OPTIM_MAX_TENSORS = 16  # UAVX_OPTIM_MAX_TENSORS
+# every symbol include/uavx_replay.h declares
+REPLAY_SYMBOLS = ("uavx_replay_version", "uavx_replay_workspace_bytes", "uavx_replay_sample")
+REPLAY_ABI_VERSION = 1
+REPLAY_MAX_ROWS = 1048576   # UAVX_REPLAY_MAX_ROWS
+REPLAY_SINGLE_ROWS = 1024   # UAVX_REPLAY_SINGLE_ROWS: up to here one launch and no workspace
 
 _lib_handle = None
+
+
+class ReplayRing(ctypes.Structure):
+    """uavx_replay_ring of include/uavx_replay.h."""
+    _fields_ = ([(n, ctypes.c_void_p) for n in ("obs", "act", "rew", "done", "skip", "trunc", "ended")]
+                + [(n, ctypes.c_int64) for n in ("slots", "envs", "agents", "learners")])
 
 
 def _sources():
     import glob
     return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER])
+            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER])
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the four headers of include/, plus
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the five headers of include/, plus
     the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
     return _native.source_hash(CSRC, _sources())
 
@@ -108,6 +121,12 @@ def load():
     f64, pvp, pi64 = ctypes.c_double, ctypes.POINTER(vp), ctypes.POINTER(i64)
     L.uavx_optim_adam.argtypes = [i32, pvp, pvp, pvp, pvp, pvp, pvp, pi64, f64, f64, f64, f64, f64, vp, vp, vp]
     L.uavx_optim_soft_update.argtypes = [i32, pvp, pvp, pi64, f64, vp]
+    L.uavx_replay_version.restype = i32
+    if L.uavx_replay_version() != REPLAY_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks replay ABI version {L.uavx_replay_version()}, this package binds "
+                           f"{REPLAY_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_replay_workspace_bytes.argtypes = [i64, pi64]
+    L.uavx_replay_sample.argtypes = [ctypes.POINTER(ReplayRing), i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
     _lib_handle = L
     return L
 

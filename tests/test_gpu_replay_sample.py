@@ -1,0 +1,319 @@
+"""FusedReplaySampler (libuavx_actor.so, include/uavx_replay.h) on the MI355X: bit-identical to DeviceReplay.sample on rings
+written by a real env (before and after the wrap, learner subsets, packed flags, manual resets, no valid row at all), and to
+tests/replay_ref.py on crafted rings and uniforms (fallback runs across wave, block and launch boundaries, uniforms outside
+[0, 1) next to poisoned memory), preallocated outputs feeding the fused learner kernels, and graph capture that follows the
+ring through a device-side count."""
+import copy
+
+import numpy as np
+import pytest
+import torch
+
+import replay_ref
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda", 0)
+E, N, T = 8, 4, 5
+L = T + 1
+ROWS = (1, 63, 64, 65, 256, 1024, 1025, 4099)
+
+
+def _mem(steps, learners=None, packed=False, seed=3):
+    """A ring written by `steps` real env steps with step_cap=3 and auto-reset: about a quarter of its cells are reset rows."""
+    from gym_uav_collision_avoidance_amd import BatchedMultiUAVWorld2D
+    from gym_uav_collision_avoidance_amd.replay import DeviceReplay
+    env = BatchedMultiUAVWorld2D(E, num_agents=N, device=DEV, seed=seed)
+    mem = DeviceReplay(env, horizon=T, num_learners=learners, packed_flags=packed)
+    mem.begin(env.reset())
+    _step(mem, steps, seed)
+    return env, mem
+
+
+def _step(mem, steps, seed=0):
+    g = torch.Generator(device=DEV).manual_seed(100 + seed)
+    for _ in range(steps):
+        mem.action_slot().copy_(torch.rand((E, N, 2), generator=g, device=DEV) * 2 - 1)
+        mem.step(polar=True, auto_reset="agent0_done", step_cap=3)
+
+
+def _sampler(mem):
+    from gym_uav_collision_avoidance_amd.fused_replay import FusedReplaySampler
+    return FusedReplaySampler(mem)
+
+
+def _same_as_mem_sample(mem, sampler, rows, seed):
+    g1, g2 = torch.Generator(device=DEV).manual_seed(seed), torch.Generator(device=DEV).manual_seed(seed)
+    want = mem.sample(rows, generator=g1, with_flags=True)
+    got = sampler.sample(rows, generator=g2, with_flags=True)
+    assert len(got) == len(want) == 7
+    for x, w in zip(got, want):
+        assert x.shape == w.shape and x.dtype == w.dtype and x.device == w.device and x.is_contiguous()
+        assert torch.equal(x, w)
+    # the generators advanced alike
+    assert torch.equal(torch.rand(7, generator=g1, device=DEV), torch.rand(7, generator=g2, device=DEV))
+    five = sampler.sample(rows, generator=torch.Generator(device=DEV).manual_seed(seed))
+    assert len(five) == 5 and all(torch.equal(x, w) for x, w in zip(five, want))
+    return want
+
+
+def _skip_of(mem):
+    return ((mem.done[:, :, 0] & 2) != 0) if mem.packed else (mem.skip != 0)
+
+
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("learners", [4, 3])
+@pytest.mark.parametrize("steps", [3, 14])
+def test_equals_device_replay_sample(steps, learners, packed):
+    env, mem = _mem(steps, learners, packed)
+    sampler = _sampler(mem)
+    assert mem.count == steps
+    if steps > T:
+        frac = float(_skip_of(mem).float().mean())
+        assert 0.1 < frac < 0.5, frac                    # reset rows exist: the redraw and the fallback have work
+    for rows in ROWS:
+        out = _same_as_mem_sample(mem, sampler, rows, seed=rows)
+        assert int(out[1].shape[0]) == rows
+    half = torch.arange(E, device=DEV) % 2 == 0
+    mem.reset(half)                                      # takes the newest transition of half the envs out of sampling
+    for rows in ROWS:
+        _same_as_mem_sample(mem, sampler, rows, seed=1000 + rows)
+    env.close()
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_no_valid_row(packed):
+    env, mem = _mem(1, packed=packed)
+    mem.reset()
+    assert bool(_skip_of(mem)[0].all()) and mem.count == 1
+    sampler = _sampler(mem)
+    for rows in (5, 1500):
+        s, a, r, s2, m, tr, en = _same_as_mem_sample(mem, sampler, rows, seed=rows)
+        for x in (s, a, r, s2, m):                       # every row is the draw of the last one
+            assert torch.equal(x, x[-1:].expand_as(x))
+    env.close()
+
+
+# ---- crafted rings and uniforms against replay_ref ---------------------------------------------------------------------
+
+def _craft(mem, count, seed=0):
+    """Overwrites the ring with unique cells and hand-set flags: every cell of env 0 is a reset row, no other is."""
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    mem.obs.copy_(torch.arange(mem.obs.numel(), device=DEV, dtype=torch.float32).view_as(mem.obs))
+    mem.act.copy_(-torch.arange(mem.act.numel(), device=DEV, dtype=torch.float32).view_as(mem.act) - 1)
+    mem.rew.copy_(torch.arange(mem.rew.numel(), device=DEV, dtype=torch.float32).view_as(mem.rew) + 0.5)
+    mem.done.copy_((torch.rand(mem.done.shape, generator=g, device=DEV) < 0.4).to(torch.uint8))
+    skip = torch.zeros((L, E), dtype=torch.uint8, device=DEV)
+    skip[:, 0] = 1
+    trunc = (torch.rand((L, E), generator=g, device=DEV) < 0.4).to(torch.uint8)
+    ended = trunc | (torch.rand((L, E), generator=g, device=DEV) < 0.3).to(torch.uint8)
+    if mem.packed:
+        mem.done[:, :, 0] |= skip * 2 + trunc * 8 + ended * 4
+    else:
+        mem.skip.copy_(skip), mem.trunc.copy_(trunc), mem.ended.copy_(ended)
+    mem.count = count
+
+
+def _arrays(mem):
+    a = dict(obs=mem.obs, act=mem.act, rew=mem.rew, done=mem.done)
+    if not mem.packed:
+        a.update(skip=mem.skip, trunc=mem.trunc, ended=mem.ended)
+    return {k: v.cpu().numpy() for k, v in a.items()}
+
+
+def _uniforms(rows, invalid, seed=0, redrawn=()):
+    """u [2, 3, rows]: rows of `invalid` draw env 0 twice, rows of `redrawn` draw it once, every other row never."""
+    rng = np.random.default_rng(seed)
+    u = rng.random((2, 3, rows), dtype=np.float32)
+    u[:, 1] = (rng.integers(1, E, size=(2, rows)) + 0.5) / E
+    inv = np.asarray(list(invalid), dtype=np.int64)
+    u[0, 1, inv] = u[1, 1, inv] = 0.5 / E
+    u[0, 1, np.asarray(list(redrawn), dtype=np.int64)] = 0.25 / E
+    return u
+
+
+def _check_ref(mem, sampler, u, **kw):
+    want = replay_ref.sample(u, count=mem.count, T=T, num_learners=mem.num_learners, **_arrays(mem))
+    got = sampler.sample_from_uniforms(torch.from_numpy(u).to(DEV), with_flags=True, **kw)
+    torch.cuda.synchronize()
+    for x, w in zip(got, want[:7]):
+        x = x.cpu().numpy()
+        assert x.shape == w.shape and x.dtype == w.dtype and np.array_equal(x, w)
+    return want
+
+
+CASES = {
+    "run_at_start": (300, range(0, 10)),
+    "run_at_end": (300, range(290, 300)),
+    "run_over_launch_limit_and_block_edge": (2048, range(1000, 1101)),
+    "only_valid_in_last_block": (3000, [j for j in range(3000) if j != 2500]),
+    "only_valid_in_first_block": (3000, [j for j in range(3000) if j != 5]),
+    "two_empty_blocks_between": (4099, range(1000, 3500)),
+    "wave_edges": (256, list(range(60, 130)) + [191, 192, 255]),
+    "none_valid": (2049, range(2049)),
+}
+
+
+@pytest.mark.parametrize("packed", [False, True])
+@pytest.mark.parametrize("case", sorted(CASES))
+def test_crafted_fallback_runs(case, packed):
+    env, mem = _mem(1, packed=packed)
+    _craft(mem, count=9)
+    rows, invalid = CASES[case]
+    invalid = set(invalid)
+    redrawn = [j for j in range(3, rows, 7) if j not in invalid]
+    u = _uniforms(rows, invalid, seed=len(case), redrawn=redrawn)
+    want = _check_ref(mem, _sampler(mem), u)
+    src = want[7]
+    valid = np.array([j not in invalid for j in range(rows)])
+    assert np.array_equal(src, replay_ref.source_rows(valid))           # the reference saw the intended pattern
+    assert (src[valid] == np.arange(rows)[valid]).all()
+    if case == "run_over_launch_limit_and_block_edge":
+        assert (src[1000:1101] == 999).all()
+    if case == "only_valid_in_last_block":
+        assert (src == 2500).all()
+    if case == "none_valid":
+        assert (src == rows - 1).all()
+    env.close()
+
+
+@pytest.mark.parametrize("count", [1, T, T + 1, 2 * T + 3])
+def test_crafted_counts_and_one_learner(count):
+    for learners in (4, 1):
+        env, mem = _mem(1, learners=learners)
+        _craft(mem, count=count)
+        sampler = _sampler(mem)
+        for rows in (300, 1100):
+            u = _uniforms(rows, range(40, 50), seed=count, redrawn=range(3, rows, 5))
+            u[:, 0, :8] = np.array([0.0, 1 - 2.0 ** -24, 0.5, 0.999999, 0.2, 0.4, 0.6, 0.8], dtype=np.float32)
+            want = _check_ref(mem, sampler, u)
+            slots = (want[0][:, 0] // (E * N * 10)).astype(np.int64)     # obs cells are arange: the slot each row came from
+            lo = max(0, count - T)
+            assert set(slots.tolist()) <= {k % L for k in range(lo, count)}
+            if learners == 1:
+                assert ((want[0][:, 0] // 10).astype(np.int64) % N == 0).all()
+        env.close()
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_uniforms_outside_the_unit_interval_stay_inside_the_ring(packed):
+    """1.0, −0.5, NaN, ±inf and 1 − 2^-24 in every plane of u: the indices follow the header's rule (below 0 and NaN give
+    0, at or past 1 the top of the range), and nothing next to the ring is read -- the ring tensors sit inside larger
+    ones filled with a sentinel."""
+    env, mem = _mem(1, learners=3, packed=packed)
+    SENT = 7.0e7
+    for name in ("obs", "act", "rew", "done", "skip", "trunc", "ended"):
+        t = getattr(mem, name)
+        big = torch.full((L + 2,) + tuple(t.shape[1:]), 255 if t.dtype == torch.uint8 else SENT, dtype=t.dtype, device=DEV)
+        setattr(mem, name, big[1:L + 1])
+        assert getattr(mem, name).is_contiguous()
+    _craft(mem, count=9)
+    sampler = _sampler(mem)
+    special = np.array([1.0, -0.5, np.nan, np.inf, -np.inf, 1 - 2.0 ** -24, 2.5, -1e30, 3e38, -0.0], dtype=np.float32)
+    u = _uniforms(64, range(20, 24), seed=5)
+    for d in range(2):
+        for c in range(3):
+            at = 2 + 10 * (d * 3 + c) % 54
+            u[d, c, at:at + 10] = special
+    u[:, :, 54:64] = special                                   # and every plane at once
+    want = _check_ref(mem, sampler, u)
+    got = sampler.sample_from_uniforms(torch.from_numpy(u).to(DEV), with_flags=True)
+    for x in got[:5]:
+        assert bool(torch.isfinite(x).all()) and not bool((x == SENT).any())
+    assert set(np.unique(want[4]).tolist()) <= {0.0, 1.0}
+    env.close()
+
+
+def test_outputs_land_in_given_buffers_and_feed_the_fused_learner():
+    from grad_ref import critic, params
+    from gym_uav_collision_avoidance_amd.fused_critic import FusedCriticLoss, FusedTarget
+    from gym_uav_collision_avoidance_amd.policy import GaussianPolicy
+    env, mem = _mem(14)
+    sampler = _sampler(mem)
+    B = 256
+    bufs = (torch.zeros((B, 10), device=DEV), torch.zeros((B, 2), device=DEV), torch.zeros(B, device=DEV),
+            torch.zeros((B, 10), device=DEV), torch.zeros(B, device=DEV), torch.zeros(B, dtype=torch.bool, device=DEV),
+            torch.zeros(B, dtype=torch.bool, device=DEV))
+    ptrs = [b.data_ptr() for b in bufs]
+    out = sampler.sample(B, generator=torch.Generator(device=DEV).manual_seed(4), out=bufs)
+    assert len(out) == 7 and [o.data_ptr() for o in out] == ptrs
+    want = mem.sample(B, generator=torch.Generator(device=DEV).manual_seed(4), with_flags=True)
+    assert all(torch.equal(x, w) for x, w in zip(bufs, want))
+    out5 = sampler.sample(B, generator=torch.Generator(device=DEV).manual_seed(4), out=bufs[:5])
+    assert len(out5) == 5 and [o.data_ptr() for o in out5] == ptrs[:5]
+    # the same uniforms twice: bitwise identical, at one launch and at two
+    for rows in (B, 2500):
+        u = torch.rand((2, 3, rows), generator=torch.Generator(device=DEV).manual_seed(rows), device=DEV)
+        a, b = sampler.sample_from_uniforms(u, with_flags=True), sampler.sample_from_uniforms(u, with_flags=True)
+        assert all(torch.equal(x, y) and x.data_ptr() != y.data_ptr() for x, y in zip(a, b))
+    # the buffers feed FusedTarget and FusedCriticLoss like mem.sample's tensors
+    torch.manual_seed(5)
+    actor = GaussianPolicy().to(DEV)
+    res = []
+    for batch in (bufs[:5], want[:5]):
+        m = critic("sac", 17, device=DEV)
+        tgt, cl = FusedTarget(actor, copy.deepcopy(m)), FusedCriticLoss(m)
+        s, a, r, s2, mk = batch
+        y = tgt(s2, r, mk, alpha=0.2, generator=torch.Generator(device=DEV).manual_seed(6))
+        cl.backward(s, a, y)
+        res.append([y.clone()] + [p.grad.clone() for p in params(m)])
+    assert all(torch.equal(x, w) for x, w in zip(*res))
+    # what the sampler refuses
+    with pytest.raises(ValueError, match="uavx: out must hold 5 tensors"):
+        sampler.sample(B, out=bufs[:4])
+    with pytest.raises(ValueError, match=r"uavx: out\[state\] must be"):
+        sampler.sample(B, out=(bufs[0][:100],) + bufs[1:5])
+    with pytest.raises(ValueError, match=r"uavx: out\[reward\] must be"):
+        sampler.sample(B, out=bufs[:2] + (bufs[2].double(),) + bufs[3:5])
+    with pytest.raises(ValueError, match=r"uavx: out\[action\] must be contiguous"):
+        sampler.sample(B, out=(bufs[0], torch.zeros((B, 4), device=DEV)[:, :2]) + bufs[2:5])
+    with pytest.raises(ValueError, match=r"uavx: out\[mask\] is on cpu"):
+        sampler.sample(B, out=bufs[:4] + (torch.zeros(B),))
+    with pytest.raises(ValueError, match="uavx: FusedReplaySampler takes 0..1048576 rows"):
+        sampler.sample(2 ** 20 + 1)
+    with pytest.raises(ValueError, match="uavx: the uniforms must be"):
+        sampler.sample_from_uniforms(torch.zeros((3, 2, 8), device=DEV))
+    env2, empty = _mem(0)
+    with pytest.raises(ValueError, match="uavx: the replay memory is empty"):
+        _sampler(empty).sample(B)
+    env.close(), env2.close()
+
+
+def test_graph_capture_follows_the_device_count():
+    env, mem = _mem(3)
+    B = 2048
+    sampler = _sampler(mem).reserve(B)
+    u_np = _uniforms(B, (), seed=8)
+    u_np[:, 1] = np.random.default_rng(9).random((2, B), dtype=np.float32)      # real reset rows decide validity
+    u = torch.from_numpy(u_np).to(DEV)
+    bufs = (torch.zeros((B, 10), device=DEV), torch.zeros((B, 2), device=DEV), torch.zeros(B, device=DEV),
+            torch.zeros((B, 10), device=DEV), torch.zeros(B, device=DEV), torch.zeros(B, dtype=torch.bool, device=DEV),
+            torch.zeros(B, dtype=torch.bool, device=DEV))
+    sampler.push_count()
+    sampler.sample_from_uniforms(u, out=bufs, device_count=True)                # warm-up outside the capture
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        sampler.sample_from_uniforms(u, out=bufs, device_count=True)
+    for extra in (0, 2, 4):                              # count 3, 5 (= T) and 7 (wrapped)
+        _step(mem, 2 if extra else 0, seed=extra)
+        sampler.push_count()
+        for b in bufs:
+            b.zero_()
+        graph.replay()
+        torch.cuda.synchronize()
+        assert mem.count == 3 + extra
+        want = replay_ref.sample(u_np, count=mem.count, T=T, num_learners=mem.num_learners, **_arrays(mem))
+        for x, w in zip(bufs, want[:7]):
+            assert np.array_equal(x.cpu().numpy(), w)
+        assert (want[7] != np.arange(B)).any() or extra == 0
+    # a capture cannot allocate the workspace of a large batch
+    fresh = _sampler(mem)
+    scratch = torch.zeros(8, device=DEV)
+    g2 = torch.cuda.CUDAGraph()
+    with pytest.raises(RuntimeError, match="uavx: the workspace for 2048 rows must exist before a graph capture"):
+        with torch.cuda.graph(g2):
+            scratch.add_(1)
+            fresh.sample_from_uniforms(u, out=bufs, device_count=True)
+    torch.cuda.synchronize()
+    env.close()
