@@ -46,7 +46,7 @@ __global__ __launch_bounds__(kWave * W) void step_k_kernel(MultiParams p, const 
         if (m.active) load_action<ACT64>(reinterpret_cast<const char *>(actions) + abytes, m.a, ax, ay);
         float o[10], rew;
         uint32_t dn, re, ce;
-        step_agent<NT, false>(p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce);
+        step_agent<NT, false>(p, p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce);
         reach_acc += re;
         coll_acc += ce;
         nonfin_acc += !(fabsf(rew) < INFINITY) ? 1u : 0u;

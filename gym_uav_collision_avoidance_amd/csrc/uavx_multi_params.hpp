@@ -71,6 +71,12 @@ struct WorldLims {
 // at the end costs nothing beyond its own use (5.78 with the tripwire it serves); a deliberate "hot members first, one
 // 64-byte line per phase" order was WORSE at 4 UAVs (5.93) and better with scripted bodies (16.9 vs 17.4); parameters read
 // from a device-resident block instead (one pointer in the kernel arguments) gave 5.78 / 17.7.  New members go at the END.
+// What those figures measured is WHERE the compiler's scalar loads of the struct landed relative to the wait for the state
+// loads, not the order as such.  The plain step_kernel variants no longer leave that to the compiler: they read three fixed
+// runs of the struct by offset in front of that wait (fetch_step_args, uavx_multi_step.hpp; the static_asserts below HotParams
+// pin the runs), so for them the order has stopped being a tuning parameter -- and moving a member of those runs breaks the
+// build.  Every other kernel (the variants with bodies / levels, step_ex_kernel, step_k_kernel, reset, observe) still reads the
+// struct through compiler-placed loads, and for those the note above stands.
 struct MultiParams {
     double tau, rtau, amax, vmax;  // rtau = RN(1/tau), see div_tau()
     double lox, loy, hix, hiy;
@@ -136,6 +142,24 @@ struct MultiParams {
     // (LAST on purpose, see the note above the struct.)
     uint32_t *nonfin;
 };
+// What one agent step reads on its straight-line path, as VALUES: step_agent() and its helpers take these instead of reading
+// a fixed struct (template parameter H), so a kernel decides where they come from: MultiParams itself is the plain form (the
+// compiler places the scalar loads of the argument segment, as for any other member); step_kernel fetches a HotParams itself in
+// front of its first wait (fetch_step_args).  Same member names as MultiParams.
+struct HotParams {
+    double tau, rtau, amax, vmax, speed_sq_lim;
+    float lo_x, lo_y, hi_x, hi_y;
+    float sq_sense, sq_two_r, sq_hard, inv_sense, vmax_norm, inv_vmax_norm, inv_diag;
+    int recip_ok;
+};
+// fetch_step_args reads MultiParams as three runs of dwords; the runs are pinned here, so a moved member fails the build
+static_assert(offsetof(MultiParams, tau) == 0 && offsetof(MultiParams, rtau) == 8 && offsetof(MultiParams, amax) == 16 &&
+              offsetof(MultiParams, vmax) == 24, "fetch_step_args: the kinematics run");
+static_assert(offsetof(MultiParams, lo_x) == 64 && offsetof(MultiParams, lo_y) == 68 && offsetof(MultiParams, hi_x) == 72 &&
+              offsetof(MultiParams, hi_y) == 76 && offsetof(MultiParams, speed_sq_lim) == 80 && offsetof(MultiParams, sq_sense) == 88 &&
+              offsetof(MultiParams, sq_two_r) == 92 && offsetof(MultiParams, sq_hard) == 96 && offsetof(MultiParams, inv_sense) == 100 &&
+              offsetof(MultiParams, vmax_norm) == 104 && offsetof(MultiParams, inv_vmax_norm) == 108 &&
+              offsetof(MultiParams, inv_diag) == 112 && offsetof(MultiParams, recip_ok) == 120, "fetch_step_args: the limits run");
 constexpr uint32_t kStageValid = 0x80000000u;
 constexpr uint32_t kRecEnded = 0x80000000u;  // env_rec.y bit 31: episode ended, re-initialise at the next step_ex
 constexpr uint32_t kFlagInactive = UAVX_FLAG_INACTIVE;

@@ -114,13 +114,14 @@ struct LdsTiles {
 // table every lane of the chip shares, i.e. an L1/L2 hit whose latency hides under the kinematics.
 // d_sense alone (all the neighbour scan needs): the other seven limits are fetched AFTER the scan, where they are used --
 // per-lane values loaded at the top of the step stayed in eight registers across the scan, the most register-hungry stretch
-template <bool EXT>
-__device__ __forceinline__ float sense_limit(const MultiParams &p, uint32_t flags) {
+// (h: the handle's own limits as the caller holds them -- `p` itself, or step_kernel's fetched copies, HotParams)
+template <bool EXT, class H>
+__device__ __forceinline__ float sense_limit(const MultiParams &p, const H &h, uint32_t flags) {
     if (EXT && p.n_levels > 0) return p.levels[(flags & kLevelMask) >> kLevelShift].sq_sense;
-    return p.sq_sense;
+    return h.sq_sense;
 }
-template <bool EXT>
-__device__ __forceinline__ WorldLims world_lims(const MultiParams &p, uint32_t flags) {
+template <bool EXT, class H>
+__device__ __forceinline__ WorldLims world_lims(const MultiParams &p, const H &h, uint32_t flags) {
     WorldLims w;
     if (EXT && p.n_levels > 0) {   // uniform: no curriculum installed -> the handle's own world, as in the plain kernels
         const float4 *t = reinterpret_cast<const float4 *>(&p.levels[(flags & kLevelMask) >> kLevelShift]);
@@ -128,10 +129,14 @@ __device__ __forceinline__ WorldLims world_lims(const MultiParams &p, uint32_t f
         w.lo_x = a.x; w.lo_y = a.y; w.hi_x = a.z; w.hi_y = a.w;
         w.sq_sense = b.x; w.sq_two_r = b.y; w.inv_sense = b.z; w.inv_diag = b.w;
     } else {
-        w.lo_x = p.lo_x; w.lo_y = p.lo_y; w.hi_x = p.hi_x; w.hi_y = p.hi_y;
-        w.sq_sense = p.sq_sense; w.sq_two_r = p.sq_two_r; w.inv_sense = p.inv_sense; w.inv_diag = p.inv_diag;
+        w.lo_x = h.lo_x; w.lo_y = h.lo_y; w.hi_x = h.hi_x; w.hi_y = h.hi_y;
+        w.sq_sense = h.sq_sense; w.sq_two_r = h.sq_two_r; w.inv_sense = h.inv_sense; w.inv_diag = h.inv_diag;
     }
     return w;
+}
+template <bool EXT>
+__device__ __forceinline__ WorldLims world_lims(const MultiParams &p, uint32_t flags) {
+    return world_lims<EXT>(p, p, flags);
 }
 
 // Agent slots are addressed with 32-bit lane offsets from scalar base pointers (saddr + voffset
@@ -155,14 +160,19 @@ __device__ __forceinline__ void load_agent(const MultiParams &p, uint32_t a, Age
 // flags_in: the flags word as loaded (the word is stored only if the step changed it)
 // (pos / vel / goal: p's arrays, handed over separately because the register-tight kernels fetch those pointers again at
 //  their end instead of holding them in scalar registers from the loads at the top on, see LATE())
-__device__ __forceinline__ void store_agent(const MultiParams &p, float2 *pos, double2 *vel, Goal *goal, uint32_t a,
-                                            const AgentRegs &s, uint32_t flags_in) {
+// (nslot = E * N, from whichever kernel arguments the caller has at hand)
+__device__ __forceinline__ void store_agent(uint32_t nslot, float2 *pos, double2 *vel, Goal *goal, uint32_t a, const AgentRegs &s,
+                                            uint32_t flags_in) {
     // velocity: 16 B per lane, written through (sc1) like the obs tile so that it drains during the launch instead
     // of at the kernel boundary (A/B at 65536x4: 6.71 -> 6.21 us); the 8-byte position store stays plain
     // (narrow sc1 stores are slow: 6.29 us with both)
-    store16_wt(make_rsrc(vel, (uint32_t)p.E * (uint32_t)p.N * 16u), a * 16u, make_double2(s.vx, s.vy));
+    store16_wt(make_rsrc(vel, nslot * 16u), a * 16u, make_double2(s.vx, s.vy));
     pos[a] = make_float2(s.x, s.y);
     if (s.flags != flags_in) goal[a].flags = s.flags;
+}
+__device__ __forceinline__ void store_agent(const MultiParams &p, float2 *pos, double2 *vel, Goal *goal, uint32_t a,
+                                            const AgentRegs &s, uint32_t flags_in) {
+    store_agent((uint32_t)p.E * (uint32_t)p.N, pos, vel, goal, a, s, flags_in);
 }
 __device__ __forceinline__ void store_agent(const MultiParams &p, uint32_t a, const AgentRegs &s, uint32_t flags_in) {
     store_agent(p, p.pos, p.vel, p.goal, a, s, flags_in);

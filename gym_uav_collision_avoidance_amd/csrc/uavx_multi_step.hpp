@@ -2,11 +2,11 @@
 // step_kernel.  Included by uavx_multi.hip inside namespace uavx, after uavx_multi_scan.hpp.
 
 // MUW:60-109 in float32 (angles compared on the circle; see DESIGN.md numerics).
-template <class LDS>
-__device__ __forceinline__ void assemble_obs(const MultiParams &p, const WorldLims &w, const LaneMap &m, const LDS &lds,
+template <class LDS, class H>
+__device__ __forceinline__ void assemble_obs(const H &h, const WorldLims &w, const LaneMap &m, const LDS &lds,
                                              const Neigh &nb, float nx, float ny, float speed, float theta, float dist_t,
                                              float dth, float o[10]) {
-    o[0] = speed * p.inv_vmax_norm;  // MUW:62
+    o[0] = speed * h.inv_vmax_norm;  // MUW:62
     o[1] = theta * kInvPi;           // MUW:64
     o[2] = dist_t * w.inv_diag;      // MUW:68
     o[3] = dth * kInvPi;             // MUW:72
@@ -32,8 +32,8 @@ __device__ __forceinline__ void assemble_obs(const MultiParams &p, const WorldLi
 // Even N: a0 and cnt are even, so the block is 16-byte aligned and a whole number of float4
 // (uavx_create/step check the 16-byte alignment of the caller's obs pointer); otherwise float2.
 template <int NT, class LDS>
-__device__ __forceinline__ void store_obs_block(const MultiParams &p, const LaneMap &m, LDS &lds, const float o[10],
-                                                float *obs_out) {
+__device__ __forceinline__ void store_obs_block(uint32_t nslot, int n_agents, const LaneMap &m, LDS &lds, const float o[10],
+                                                float *obs_out) {   // nslot = E * N, n_agents = N (read when NT == 0)
     constexpr int T = kWave * LDS::kW;
     float *stage = lds.obs + m.obs0;
     if (m.active) {
@@ -43,9 +43,9 @@ __device__ __forceinline__ void store_obs_block(const MultiParams &p, const Lane
     }
     group_sync<LDS::kW>();
     const int nfloat = m.cnt * UAVX_OBS_DIM;
-    const rsrc_t r = make_rsrc(obs_out, (uint32_t)p.E * (uint32_t)p.N * (UAVX_OBS_DIM * 4u));
+    const rsrc_t r = make_rsrc(obs_out, nslot * (UAVX_OBS_DIM * 4u));
     const uint32_t gbase = m.a0 * (UAVX_OBS_DIM * 4u);  // byte offset of the workgroup's block
-    if (NT ? (NT % 2 == 0) : ((p.N & 1) == 0)) {   // uniform: even N => 16-byte aligned block of whole float4
+    if (NT ? (NT % 2 == 0) : ((n_agents & 1) == 0)) {   // uniform: even N => 16-byte aligned block of whole float4
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const int f = (k * T + m.lane) * 4;
@@ -71,6 +71,11 @@ __device__ __forceinline__ void store_obs_block(const MultiParams &p, const Lane
         if (m.lane == 1 && tail < nfloat) store8_wt(r, gbase + (uint32_t)tail * 4u, *reinterpret_cast<const float2 *>(stage + tail));
     }
     group_sync<LDS::kW>();
+}
+template <int NT, class LDS>
+__device__ __forceinline__ void store_obs_block(const MultiParams &p, const LaneMap &m, LDS &lds, const float o[10],
+                                                float *obs_out) {
+    store_obs_block<NT>((uint32_t)p.E * (uint32_t)p.N, p.N, m, lds, o, obs_out);
 }
 
 // configs[4] extension: a body starts a leg at (x, y) towards waypoint (wx, wy) -- include/uavx.h, uavx_set_body_rule; float32,
@@ -139,20 +144,22 @@ __device__ __forceinline__ void stage_bodies(const MultiParams &p, const LaneMap
 //   frozen: the env was re-initialised by this call (auto-reset); the agent only observes.
 //   EXT: env_steps / ep_draw = the env's step count before this step and the episode index its reset drew with
 //        (scripted bodies); frozen envs had their bodies' rows staged by the reset path.
-template <int NT, bool EXT, class LDS, bool LATEW = false, bool SQ = false>   // SQ: see scan_neighbours
-__device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &m, LDS &lds, AgentRegs &s, double ax,
+//   h: where the straight-line path reads the handle's parameters: `p` itself (compiler-placed loads of the argument segment) or
+//      a HotParams the kernel fetched (step_kernel); same member names
+template <int NT, bool EXT, class LDS, bool LATEW = false, bool SQ = false, class H = MultiParams>   // SQ: see scan_neighbours
+__device__ __forceinline__ void step_agent(const MultiParams &p, const H &h, const LaneMap &m, LDS &lds, AgentRegs &s, double ax,
                                            double ay, int evaluate, float o[10], float &rew, uint32_t &done_out,
                                            uint32_t &reach_ev, uint32_t &coll_ev, bool frozen = false,
                                            uint32_t env_steps = 0, uint32_t ep_draw = 0) {
-    const float sq_sense = sense_limit<EXT>(p, s.flags);
+    const float sq_sense = sense_limit<EXT>(p, h, s.flags);
     const bool was_done = (s.flags & UAVX_FLAG_DONE) != 0;
     const bool parked = EXT && (s.flags & kFlagInactive) != 0;  // extension: learner switched off by its env's level
     if (!frozen) s.flags &= ~(kFlagPrevOvr | kFlagJustDone);  // from here on prev_distance is the natural one again
     const float ox = s.x, oy = s.y;
     float pd = 0.f, d = 0.f;  // AG:24-25: a done agent returns (0, 0) and does not move
     if (!was_done && !frozen && !parked) {
-        axis_update(ax, p.tau, p.rtau, p.recip_ok != 0, p.amax, p.vmax, s.vx, s.x);  // AG:26-29
-        axis_update(ay, p.tau, p.rtau, p.recip_ok != 0, p.amax, p.vmax, s.vy, s.y);
+        axis_update(ax, h.tau, h.rtau, h.recip_ok != 0, h.amax, h.vmax, s.vx, s.x);  // AG:26-29
+        axis_update(ay, h.tau, h.rtau, h.recip_ok != 0, h.amax, h.vmax, s.vy, s.y);
         pd = s.prev_d;                                       // AG:32
     }
     const float tdx = s.tx - s.x, tdy = s.ty - s.y;
@@ -169,12 +176,12 @@ __device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &
     if (EXT && p.B > 0) stage_bodies<true, LDS, LATEW>(p, m, lds, s.flags, frozen, env_steps, ep_draw);
     group_sync<LDS::kW>();
     const Neigh nb = scan_neighbours<NT, true, LDS, SQ>(sq_sense, m, lds, s.x, s.y);
-    const WorldLims w = world_lims<EXT>(p, s.flags);
+    const WorldLims w = world_lims<EXT>(p, h, s.flags);
 
     // reward shaping, MUW:188-195 (float32, reciprocals instead of divisions; |error| << 1e-5)
     const float inv_init = __builtin_amdgcn_rcpf(s.init_d);
-    float r = -0.01f * fminf(p.vmax_norm * inv_init, 1.0f);  // MUW:189
-    r += (50.0f * p.inv_vmax_norm) * (pd - d);               // MUW:190 (pd - d is a float32 subtraction there too)
+    float r = -0.01f * fminf(h.vmax_norm * inv_init, 1.0f);  // MUW:189
+    r += (50.0f * h.inv_vmax_norm) * (pd - d);               // MUW:190 (pd - d is a float32 subtraction there too)
     const float frac = d * inv_init * (1.0f / 1.5f);         // MUW:192,194
     r *= (r > 0.f) ? (1.0f - frac) : (1.0f + frac);
     r -= 0.01f * fabsf(dth);                                 // MUW:195
@@ -183,7 +190,7 @@ __device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &
     const bool collision = nb.step_sq_min <= w.sq_two_r;     // MUW:203  dist <= 2R
     if (collision) r = -2.0f;                                // MUW:204
     coll_ev = 0;
-    if (nb.step_sq_min <= p.sq_hard && !(s.flags & (UAVX_FLAG_DONE | UAVX_FLAG_COLLIDED)) && !frozen) {  // MUW:207-208
+    if (nb.step_sq_min <= h.sq_hard && !(s.flags & (UAVX_FLAG_DONE | UAVX_FLAG_COLLIDED)) && !frozen) {  // MUW:207-208
         coll_ev = 1;                                         // MUW:209
         s.flags |= UAVX_FLAG_COLLIDED;                       // MUW:210
     }
@@ -195,7 +202,7 @@ __device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &
     if (frozen) {
         done_out = 0;
         r = 0.f;
-    } else if (d < 0.5f && !collision && sq < p.speed_sq_lim) {     // MUW:218
+    } else if (d < 0.5f && !collision && sq < h.speed_sq_lim) {     // MUW:218
         done_out = 1;
         reach_ev = was_done ? 0u : 1u;                       // MUW:220-221
         s.flags |= UAVX_FLAG_DONE | (was_done ? 0u : kFlagJustDone);  // AG:39
@@ -212,7 +219,7 @@ __device__ __forceinline__ void step_agent(const MultiParams &p, const LaneMap &
     }
     if (!frozen) s.prev_d = d;                               // MUW:229
     rew = r;
-    assemble_obs(p, w, m, lds, nb, s.x, s.y, speed, theta, dist_t, dth, o);  // MUW:233-235
+    assemble_obs(h, w, m, lds, nb, s.x, s.y, speed, theta, dist_t, dth, o);  // MUW:233-235
     if (parked) {  // extension: a parked learner reports an all-zero observation, no reward, done
 #pragma unroll
         for (int k = 0; k < UAVX_OBS_DIM; k++) o[k] = 0.f;
@@ -236,21 +243,76 @@ __device__ __forceinline__ void load_action(const void *__restrict__ actions, ui
 // The arguments the FIRST instructions need -- command pointer, the base of the state allocation and the 32-bit offsets of its
 // arrays, the numbers the lane mapping is made of -- are LEADING SCALAR kernel arguments: gfx950 preloads those into SGPRs before
 // the wavefront starts (Makefile: -mllvm -amdgpu-kernarg-preload-count), so the state loads are the first thing a wavefront does
-// instead of waiting for a scalar load of the argument segment; everything else of the argument struct is fetched behind them
-// (scheduling barrier).  A/B, same library, three runs each (profiles/r04_ab_notes.md section 10): 65 536 x 4 5.76 -> 5.56 us,
-// x 8 10.4 -> 10.0, x 2 4.19 -> 4.09, 32 768 x 4 4.53 -> 4.35.
+// instead of waiting for a scalar load of the argument segment.  A/B, same library, three runs each (profiles/r04_ab_notes.md
+// section 10): 65 536 x 4 5.76 -> 5.56 us, x 8 10.4 -> 10.0, x 2 4.19 -> 4.09, 32 768 x 4 4.53 -> 4.35.
+// The REST of the argument struct: a scheduling barrier behind the state loads was meant to put its scalar loads behind them.
+// What the compiler emitted was those loads behind the WAIT for the state loads (it places a load of the invariant segment at
+// its first use, and the barrier only fences what is in front of it): eleven s_load between the first `s_waitcnt vmcnt(0)` and
+// the first LDS write of the 4-UAV kernel, the one for tau / rtau / amax / vmax followed at once by `s_waitcnt lgkmcnt(0)` -- a
+// second round trip that every wavefront of the launch's single round paid at the same moment.  The plain variants (step_fetches)
+// now fetch what the straight-line path needs THEMSELVES, between the state loads and that wait (fetch_step_args), and read
+// nothing else of the arguments outside rare branches; tests/test_step_isa_host.py holds the instruction order.
+// The variants with bodies / levels keep the compiler-placed loads.  Numbers: profiles/r12_karg_ab.md.
 // (with bodies the allocator lands on 65 VGPRs = 7 wavefronts per SIMD; asking for 8 gives 62 without a spill)
 #ifndef UAVX_STEPB
 #define UAVX_STEPB 8
 #endif
+// What step_kernel's straight-line path needs of its argument segment, fetched by the kernel itself: three scalar loads through
+// the laundered segment pointer (late_kargs), issued behind the state loads and in front of the wait for them.
+//   dwordx8  at p.tau    tau, rtau, amax, vmax
+//   dwordx16 at p.lo_x   lo_x .. hi_y, speed_sq_lim, sq_sense .. inv_diag, (two_r_reset,) recip_ok, (N)
+//   dwordx8  behind p    evaluate, (padding,) obs_out, rew_out, done_out
+// The body then reads these copies ONLY: one remaining read of `p.tau` or `rew_out` hands the compiler a second, invariant load
+// that it places where it likes.  The rare branches (prev_ovr, the reach / coll / nonfin counters) fetch their pointer inside
+// the branch.
+constexpr uint32_t kStepLead = 56;   // MultiParams' place in step_kernel's argument segment (behind the preloaded scalars)
+typedef uint32_t karg_x8 __attribute__((ext_vector_type(8), aligned(4)));
+typedef uint32_t karg_x16 __attribute__((ext_vector_type(16), aligned(4)));
+struct StepArgs {
+    HotParams h;
+    int evaluate;
+    float *obs_out, *rew_out;
+    uint8_t *done_out;
+};
+__device__ __forceinline__ double karg_f64(uint32_t lo, uint32_t hi) { return __hiloint2double((int)hi, (int)lo); }
+template <class T>
+__device__ __forceinline__ T *karg_ptr64(uint32_t lo, uint32_t hi) { return reinterpret_cast<T *>(((uint64_t)hi << 32) | lo); }
+__device__ __forceinline__ StepArgs fetch_step_args() {
+    const karg_ptr ka = late_kargs();
+    const karg_x8 k = late_karg<karg_x8>(kStepLead + (uint32_t)offsetof(MultiParams, tau), ka);
+    const karg_x16 l = late_karg<karg_x16>(kStepLead + (uint32_t)offsetof(MultiParams, lo_x), ka);
+    const karg_x8 io = late_karg<karg_x8>(kStepLead + (uint32_t)sizeof(MultiParams), ka);
+    // an (empty) reader of all three, HERE: without it the compiler sinks each load to its first use, behind the wait for the state
+    asm volatile("" ::"s"(k), "s"(l), "s"(io));
+    StepArgs a;
+    a.h.tau = karg_f64(k[0], k[1]); a.h.rtau = karg_f64(k[2], k[3]); a.h.amax = karg_f64(k[4], k[5]); a.h.vmax = karg_f64(k[6], k[7]);
+    a.h.lo_x = __uint_as_float(l[0]); a.h.lo_y = __uint_as_float(l[1]); a.h.hi_x = __uint_as_float(l[2]); a.h.hi_y = __uint_as_float(l[3]);
+    a.h.speed_sq_lim = karg_f64(l[4], l[5]);
+    a.h.sq_sense = __uint_as_float(l[6]); a.h.sq_two_r = __uint_as_float(l[7]); a.h.sq_hard = __uint_as_float(l[8]);
+    a.h.inv_sense = __uint_as_float(l[9]); a.h.vmax_norm = __uint_as_float(l[10]); a.h.inv_vmax_norm = __uint_as_float(l[11]);
+    a.h.inv_diag = __uint_as_float(l[12]);
+    a.h.recip_ok = (int)l[14];
+    a.evaluate = (int)io[0];
+    a.obs_out = karg_ptr64<float>(io[2], io[3]); a.rew_out = karg_ptr64<float>(io[4], io[5]); a.done_out = karg_ptr64<uint8_t>(io[6], io[7]);
+    return a;
+}
+static_assert(sizeof(MultiParams) % 8 == 0, "fetch_step_args: `int evaluate` starts where MultiParams ends, the three pointers 8 bytes on");
+// Which variants fetch that way (-DUAVX_KFETCH=0: none, A/B).  The plain one-wavefront-tile variants do.  The variants with
+// scripted bodies / levels do not: they sit at 78 scalar registers with six already parked in VGPR lanes, and 32 more held from
+// the top would cost them their eighth wavefront.
+#ifndef UAVX_KFETCH
+#define UAVX_KFETCH 1
+#endif
+template <int NT, bool EXT, int W, int T>
+constexpr bool step_fetches() { return UAVX_KFETCH && !EXT; }
 // T > 1: T independent one-wavefront tiles per workgroup (own LDS slice, wavefront-level ordering only) -- fewer workgroups for
 // the dispatcher to place.  Pays only where one-wavefront workgroups fill every slot exactly once and live short (65 536 x 8:
 // the 2.3 us over which 8 192 workgroups are placed is a large share of a 6 us wavefront); see tiles_for().
 template <int NT, bool ACT64, bool EXT, int W, int T = 1>
 __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) void step_kernel(
     const void *__restrict__ actions, char *slab, uint32_t off_vel, uint32_t off_goal, uint32_t off_rec, uint32_t off_wsteps,
-    uint32_t num_envs, uint32_t n_agents, uint32_t envs_per_group, uint32_t magic, uint32_t nslots, MultiParams p, int evaluate,
-    float *__restrict__ obs_out, float *__restrict__ rew_out, uint8_t *__restrict__ done_out) {
+    uint32_t num_envs, uint32_t n_agents, uint32_t envs_per_group, uint32_t magic, uint32_t nslots, MultiParams p, int evaluate_arg,
+    float *__restrict__ obs_arg, float *__restrict__ rew_arg, uint8_t *__restrict__ done_arg) {
     static_assert(T == 1 || W == 1, "tiles are one-wavefront workgroups side by side");
     using LDS = std::conditional_t<(T > 1), LdsTiles<T>, LdsT<EXT, W>>;
     static_assert(T == 1 || !EXT, "tiles: the plain variants only");
@@ -259,6 +321,7 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
     // 4 UAVs, one step: state rows through buffer resources (16 scalar registers for the four of them; the other variants have none
     // to spare) and the squared-distance neighbour scan (scan_neighbours)
     constexpr bool BUF = NT == 4 && !EXT && T == 1;
+    constexpr bool FETCH = step_fetches<NT, EXT, W, T>();
     float2 *const pos_b = reinterpret_cast<float2 *>(slab);
     double2 *const vel_b = reinterpret_cast<double2 *>(slab + off_vel);
     Goal *const goal_b = reinterpret_cast<Goal *>(slab + off_goal);
@@ -273,6 +336,7 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
     double ax = 0.0, ay = 0.0;
     uint4 rec = make_uint4(0, 0, 0, 0);
     uint32_t wave_count = 0;
+    StepArgs ka = {};   // (FETCH only)
     {
         // Unconditional (idle lanes of the last workgroup read slot 0 and drop what they compute): the requests leave in front
         // of every scalar load of the argument struct.  The command goes first: prev_distance is arithmetic on the state, and
@@ -289,6 +353,7 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
             const float2 d = pos_b[al];
             const double2 v = vel_b[al];
             const Goal g = goal_b[al];
+            if constexpr (FETCH) ka = fetch_step_args();
             __builtin_amdgcn_sched_barrier(0);
             s.x = d.x; s.y = d.y; s.vx = v.x; s.vy = v.y;
             s.tx = g.tx; s.ty = g.ty; s.init_d = g.init_d; s.flags = g.flags;
@@ -303,6 +368,7 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
             const u32x2 d = __builtin_amdgcn_raw_buffer_load_b64(r_pos, al * 8u, 0, 0);
             const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(r_vel, al * 16u, 0, 0);
             const u32x4 g = __builtin_amdgcn_raw_buffer_load_b128(r_goal, al * 16u, 0, 0);
+            if constexpr (FETCH) ka = fetch_step_args();
             __builtin_amdgcn_sched_barrier(0);
             s.x = __uint_as_float(d.x); s.y = __uint_as_float(d.y);
             s.vx = __hiloint2double(v.y, v.x); s.vy = __hiloint2double(v.w, v.z);
@@ -311,14 +377,24 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
         s.prev_d = natural_prev_d(s.flags, s.x, s.y, s.tx, s.ty);
         if (m.active && (s.flags & kFlagPrevOvr)) s.prev_d = p.prev_ovr[m.a];  // rare: only after a caller poked the state
     }
+    float *const obs_out = FETCH ? ka.obs_out : obs_arg, *const rew_out = FETCH ? ka.rew_out : rew_arg;
+    uint8_t *const done_out = FETCH ? ka.done_out : done_arg;
+    const int evaluate = FETCH ? ka.evaluate : evaluate_arg;
     const uint32_t flags_in = s.flags;
     float o[10], rew;
     uint32_t dn, re, ce;
-    step_agent<NT, EXT, LDS, false, BUF>(p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, false, wave_count - rec.x,
-                                    ((rec.y & ~kRecEnded) - 1u) & ~kRecEnded);
+    if constexpr (FETCH)
+        step_agent<NT, EXT, LDS, false, BUF>(p, ka.h, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, false, wave_count - rec.x,
+                                             ((rec.y & ~kRecEnded) - 1u) & ~kRecEnded);
+    else
+        step_agent<NT, EXT, LDS, false, BUF>(p, p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, false, wave_count - rec.x,
+                                             ((rec.y & ~kRecEnded) - 1u) & ~kRecEnded);
     if (m.active) {
         if (!BUF) {
-            if (!(EXT && (flags_in & kFlagInactive))) store_agent(p, pos_b, vel_b, goal_b, m.a, s, flags_in);
+            if (!(EXT && (flags_in & kFlagInactive))) {
+                if constexpr (FETCH) store_agent(nslot, pos_b, vel_b, goal_b, m.a, s, flags_in);
+                else store_agent(p, pos_b, vel_b, goal_b, m.a, s, flags_in);
+            }
             rew_out[m.a] = rew;
             done_out[m.a] = (uint8_t)dn;
         } else {   // store_agent() through the buffer resources of the loads
@@ -329,14 +405,17 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), make_rsrc(rew_out, nslot * 4u), m.a * 4u, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)dn, make_rsrc(done_out, nslot), m.a, 0, 0);
         }
-        if (re) atomicAdd(&p.reach[m.e], 1u);                // MUW:221
-        if (ce) atomicAdd(&p.coll[m.e], 1u);                 // MUW:209
-        if (!(fabsf(rew) < INFINITY)) atomicAdd(&p.nonfin[m.e], 1u);   // the tripwire of test_ddpg_multi.py:114-130, per env
+        // (FETCH: the counters' pointers are fetched inside their rare branches)
+        if (re) atomicAdd(&karg_if<FETCH>(p.reach, kStepLead + (uint32_t)offsetof(MultiParams, reach))[m.e], 1u);   // MUW:221
+        if (ce) atomicAdd(&karg_if<FETCH>(p.coll, kStepLead + (uint32_t)offsetof(MultiParams, coll))[m.e], 1u);     // MUW:209
+        if (!(fabsf(rew) < INFINITY))   // the tripwire of test_ddpg_multi.py:114-130, per env
+            atomicAdd(&karg_if<FETCH>(p.nonfin, kStepLead + (uint32_t)offsetof(MultiParams, nonfin))[m.e], 1u);
         if (m.lane == 0) {
             uint32_t *const ws = reinterpret_cast<uint32_t *>(slab + off_wsteps);
             if (EXT) ws[m.wave] = wave_count + 1u;             // single writer: this wave (MUW:238)
             else atomicAdd(&ws[m.wave], 1u);                   // MUW:238 for every env of this wave (no-return)
         }
     }
-    store_obs_block<NT>(p, m, lds, o, obs_out);
+    if constexpr (FETCH) store_obs_block<NT>(nslot, (int)n_agents, m, lds, o, obs_out);   // (E, N: the preloaded leading scalars)
+    else store_obs_block<NT>(p, m, lds, o, obs_out);
 }

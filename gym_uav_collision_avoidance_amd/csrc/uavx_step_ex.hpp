@@ -226,7 +226,7 @@ __global__ __launch_bounds__(kWave * W * T, (W != 1) ? 1 : (EXT ? UAVX_EXB : (NT
     uint32_t dn, re, ce;
     // a freshly re-initialised env draws its bodies' waypoints with the episode index `episode`, a running one with the
     // index its own reset used (one less than the stored one)
-    step_agent<NT, EXT, LDS, (kLate & 2) != 0>(p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, do_reset, steps_v,
+    step_agent<NT, EXT, LDS, (kLate & 2) != 0>(p, p, m, lds, s, ax, ay, evaluate, o, rew, dn, re, ce, do_reset, steps_v,
                                                (episode - (do_reset ? 0u : 1u)) & ~kRecEnded);
     // episode end test for the NEXT call (test_sac_multi.py:67,112,116)
     bool all_done;

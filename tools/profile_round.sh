@@ -6,10 +6,15 @@
 #         curriculum; r: outputs into the on-device replay ring -- 65536x8+16fc4r is bench.py --cfg5)
 # Kernel trace and each counter group are separate runs (counter collection serialises and slows kernels); the
 # program itself follows `--` (no env / bash -c hop).  TCC has 4 counter slots per pass, SQ 8.
+# Every profiled run has its own time limit (STEP_TIMEOUT seconds, default 300); the first one that fails, faults or runs out of
+# time ends the script (set -e): nothing else is started on that GPU.  PROF_OUT: another output directory (an A/B arm run with
+# UAVX_LIB; tools/summarize_profiles.py reads the default one).
 set -e
+TL="timeout -k 10 ${STEP_TIMEOUT:-300}"
 cd "$(dirname "$0")/.."
 export TMPDIR=/tmp
 OUT=gpurun_out/prof
+[ -n "$PROF_OUT" ] && OUT=$PROF_OUT
 mkdir -p $OUT
 # what the passes were taken on: the hash bench.py compares with the loaded library's, and when (the tool writes both; nothing is keyed by hand)
 python3 -c "from gym_uav_collision_avoidance_amd import _lib; import json, datetime; json.dump({'csrc_sha': _lib.source_hash(), 'taken_utc': datetime.datetime.now(datetime.timezone.utc).strftime('%Y-%m-%dT%H:%M:%SZ')}, open('$OUT/meta.json','w'))"
@@ -25,7 +30,7 @@ for arg in "$@"; do
     [ -x tools/micro/fetch_calib ] || hipcc -O3 --offload-arch=gfx950 -o tools/micro/fetch_calib tools/micro/fetch_calib.hip
     d=$OUT/calib; rm -rf $d; mkdir -p $d
     for p in fetch write tcc_ea tcc_hit; do
-      rocprofv3 --output-format csv --kernel-trace --pmc ${PASS[$p]} -d $d/$p -o run -- tools/micro/fetch_calib > $d/$p.log 2>&1
+      $TL rocprofv3 --output-format csv --kernel-trace --pmc ${PASS[$p]} -d $d/$p -o run -- tools/micro/fetch_calib > $d/$p.log 2>&1
       find $d/$p -name "*kernel_trace.csv" -delete; find $d/$p -name "*agent_info.csv" -delete   # (gpurun copies back at most 64 MiB)
       echo "calib $p done"
     done
@@ -44,11 +49,11 @@ for arg in "$@"; do
     E=${shape%%x*}; N=${shape##*x}
     BARGS="--envs $E --agents $N --bodies $bodies --no-cpu-baseline --no-large $fused $extra"
   fi
-  rocprofv3 --output-format csv --kernel-trace --stats -d $d/kt -o run -- python3 bench.py $BARGS --steps 1000 --warmup 100 > $d/kt.log 2>&1
+  $TL rocprofv3 --output-format csv --kernel-trace --stats -d $d/kt -o run -- python3 bench.py $BARGS --steps 1000 --warmup 100 > $d/kt.log 2>&1
   find $d/kt -name "*kernel_trace.csv" -delete; find $d/kt -name "*agent_info.csv" -delete   # keep the stats summary only (64 MiB merge limit)
   echo "$arg kt done"
   for p in fetch write tcc_hit tcc_ea sq sq2; do
-    rocprofv3 --output-format csv --kernel-trace --pmc ${PASS[$p]} -d $d/$p -o run -- python3 bench.py $BARGS --steps 100 --warmup 20 --repeats 2 --mode launch > $d/$p.log 2>&1
+    $TL rocprofv3 --output-format csv --kernel-trace --pmc ${PASS[$p]} -d $d/$p -o run -- python3 bench.py $BARGS --steps 100 --warmup 20 --repeats 2 --mode launch > $d/$p.log 2>&1
     find $d/$p -name "*kernel_trace.csv" -delete; find $d/$p -name "*agent_info.csv" -delete
     echo "$arg $p done"
   done
