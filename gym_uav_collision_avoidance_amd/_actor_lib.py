@@ -1,6 +1,6 @@
 """ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h,
-include/uavx_optim.h, include/uavx_replay.h), the fused actor-inference, critic, TD-target, critic-gradient, optimiser-step
-and replay-sampling kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+include/uavx_optim.h, include/uavx_replay.h, include/uavx_action_grad.h), the fused actor-inference, critic, TD-target,
+critic-gradient, optimiser-step, replay-sampling and critic action-gradient kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
 that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
 missing library or device raises."""
 import ctypes
@@ -15,6 +15,7 @@ CRITIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic.h")
 GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic_grad.h")
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_optim.h")
 REPLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_replay.h")
+ACTION_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_action_grad.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -45,6 +46,10 @@ REPLAY_SYMBOLS = ("uavx_replay_version", "uavx_replay_workspace_bytes", "uavx_re
 REPLAY_ABI_VERSION = 1
 REPLAY_MAX_ROWS = 1048576   # UAVX_REPLAY_MAX_ROWS
 REPLAY_SINGLE_ROWS = 1024   # UAVX_REPLAY_SINGLE_ROWS: up to here one launch and no workspace
+# every symbol include/uavx_action_grad.h declares
+ACTION_GRAD_SYMBOLS = ("uavx_action_grad_version", "uavx_action_grad")
+ACTION_GRAD_ABI_VERSION = 1
+ACTION_GRAD_MAX_ROWS = 262144   # UAVX_ACTION_GRAD_MAX_ROWS
 
 _lib_handle = None
 
@@ -58,11 +63,11 @@ class ReplayRing(ctypes.Structure):
 def _sources():
     import glob
     return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER])
+            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER])
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the five headers of include/, plus
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the six headers of include/, plus
     the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
     return _native.source_hash(CSRC, _sources())
 
@@ -127,6 +132,11 @@ def load():
                            f"{REPLAY_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
     L.uavx_replay_workspace_bytes.argtypes = [i64, pi64]
     L.uavx_replay_sample.argtypes = [ctypes.POINTER(ReplayRing), i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.uavx_action_grad_version.restype = i32
+    if L.uavx_action_grad_version() != ACTION_GRAD_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks action-gradient ABI version {L.uavx_action_grad_version()}, this package "
+                           f"binds {ACTION_GRAD_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_action_grad.argtypes = [vp, i32, pvp, vp, i64, i64, vp, i64, vp, vp, vp]
     _lib_handle = L
     return L
 

@@ -1,6 +1,8 @@
 """FusedCritic and FusedTarget: the no-grad forward blocks of the reference's learners as ONE HIP launch each
 (libuavx_actor.so, include/uavx_critic.h) instead of a chain of torch layers and element-wise kernels; FusedCriticLoss: the
-gradient of the learners' critic loss in three launches (include/uavx_critic_grad.h), written into .grad.
+gradient of the learners' critic loss in three launches (include/uavx_critic_grad.h), written into .grad; FusedActionGrad:
+the critic towers of the learners' actor update, q and dq/da in one launch (include/uavx_action_grad.h); FusedActorLoss: the
+actor-loss block built on it, the actor itself staying torch autograd.
 
     critic = FusedCritic.from_module(critic_target)                # TwinQ, TD3TwinQ or DDPGCritic
     q1, q2 = critic.q(state, action)                               # what the module's forward returns
@@ -21,7 +23,7 @@ import torch
 
 from . import _actor_lib
 from .fused_actor import FusedActor
-from .policy import DDPGCritic, TD3TwinQ, TwinQ
+from .policy import DDPGActor, DDPGCritic, GaussianPolicy, TD3Actor, TD3TwinQ, TwinQ
 
 _PRECISIONS = {"f32": _actor_lib.F32, "bf16": _actor_lib.BF16}
 _KIND_NAMES = {_actor_lib.SAC: "SAC", _actor_lib.TD3: "TD3", _actor_lib.DDPG: "DDPG"}
@@ -347,6 +349,209 @@ class FusedCriticLoss:
         return (self._loss[0], self._loss[1]) if self.critic.towers == 2 else self._loss[0]
 
     def close(self):
+        if self._owned is not None:
+            self._owned.close()
+            self._owned = None
+
+
+class _ActionGradFn(torch.autograd.Function):
+    """q of the selected towers as a function of the action: forward is the one launch and keeps J = dq/da, backward is
+    sum_t g_t * J_t.  state and the critic's parameters are constants of the graph."""
+
+    @staticmethod
+    def forward(ctx, action, ag, state, mask):
+        q, j = ag.q_dqda(state, action, towers=mask)
+        ts = [t for t in range(ag.critic.towers) if mask >> t & 1]
+        ctx.jac = [j[t] for t in ts]
+        return tuple(q[t].unsqueeze(1) for t in ts)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *gs):
+        grad = gs[0] * ctx.jac[0]
+        for g, j in zip(gs[1:], ctx.jac[1:]):
+            grad = grad + g * j
+        return grad, None, None, None
+
+
+class FusedActionGrad:
+    """The critic of the learners' actor update (sac.py:72, td3.py:144, ddpg.py:77), where it is only a differentiable
+    function of the action: q_t(s, a) and the Jacobian dq_t/da of every selected tower in ONE HIP launch
+    (include/uavx_action_grad.h), with no weight gradients:
+
+        qa = FusedActionGrad(critic)              # TwinQ / TD3TwinQ / DDPGCritic (f32, on a GPU) or an f32 FusedCritic
+        q1, q2 = qa(state, actor_output)          # differentiable in the action only; TD3: q1 = qa(s, a, towers=1)
+        q, dqda = qa.q_dqda(state, action)        # [T, B] and [T, B, 2], no autograd
+
+    towers: a bit mask (bit t selects tower t; None = all towers of the critic).  The call reads the module's LIVE
+    parameters when the kernel runs (no refresh(): the critic's optimiser step before the actor update is seen), and leaves
+    the packed snapshot of a FusedCritic untouched.  Inputs must be float32 on the module's device; anything else raises.
+
+    How __call__ differs from running the module under autograd, as the reference does: its policy_loss.backward() also
+    accumulates weight gradients into every critic parameter's .grad, which the trainers clear before they use them
+    (sac.py:66 zero_grad, td3's critic_optimizer.zero_grad, ddpg.py:85-86) and which FusedCriticLoss overwrites.  Here
+    the critic's parameters and `state` receive no gradient and their .grad is not touched."""
+
+    def __init__(self, critic):
+        if isinstance(critic, FusedCritic):
+            fc, self._owned = critic, None
+        elif isinstance(critic, (TwinQ, TD3TwinQ, DDPGCritic)):
+            fc = None
+        else:
+            raise TypeError(f"uavx: FusedActionGrad takes a TwinQ, TD3TwinQ, DDPGCritic or FusedCritic, not "
+                            f"{type(critic).__name__}")
+        if fc is None:
+            w = next(critic.parameters())
+            if w.device.type != "cuda":
+                raise ValueError(f"uavx: FusedActionGrad needs the module on a GPU (cuda:N), its parameters are on {w.device}")
+            fc = FusedCritic.from_module(critic)
+            self._owned = fc
+        self.critic, self.module, self.kind, self.device = fc, fc.module, fc.kind, fc.device
+        self._lib = fc._lib
+        self._params = [p for lin in fc._layers for p in (lin.weight, lin.bias)]
+        self._pptrs = (ctypes.c_void_p * 12)()
+
+    def _mask(self, towers):
+        full = (1 << self.critic.towers) - 1
+        if towers is None:
+            return full
+        if isinstance(towers, bool) or not isinstance(towers, int):
+            raise TypeError(f"uavx: towers must be an int bit mask or None, not {type(towers).__name__}")
+        if towers < 1 or towers & ~full:
+            raise ValueError(f"uavx: towers mask {towers} selects nothing or a tower this {_KIND_NAMES[self.kind]} critic "
+                             f"({self.critic.towers} tower(s)) does not have")
+        return towers
+
+    @torch.no_grad()
+    def q_dqda(self, state, action, towers=None, out=None):
+        """(q [T, B], dqda [T, B, 2]) for T = the critic's tower count, on [B, 10] states and [B, 2] actions (any row
+        stride).  Only the selected towers' entries are written: the others keep what `out` held (without `out` they are
+        uninitialised).  out = (q, dqda): preallocated contiguous float32 buffers, e.g. for a graph capture."""
+        dev, T = self.device, self.critic.towers
+        mask = self._mask(towers)
+        rows, s_stride = _rows2(state, self.critic.obs_dim, dev, "state")
+        arows, a_stride = _rows2(action, self.critic.act_dim, dev, "action")
+        if arows != rows:
+            raise ValueError(f"uavx: state and action rows differ ({rows} vs {arows})")
+        if rows < 1 or rows > _actor_lib.ACTION_GRAD_MAX_ROWS:
+            raise ValueError(f"uavx: FusedActionGrad takes 1..{_actor_lib.ACTION_GRAD_MAX_ROWS} rows, got {rows}")
+        for p in self._params:
+            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
+                raise TypeError("uavx: FusedActionGrad reads contiguous float32 parameters on the critic's device")
+        if out is None:
+            q = torch.empty((T, rows), dtype=torch.float32, device=dev)
+            j = torch.empty((T, rows, 2), dtype=torch.float32, device=dev)
+        else:
+            q, j = out
+            for t, shape, what in ((q, (T, rows), "out[0]"), (j, (T, rows, 2), "out[1]")):
+                _check_f32(t, dev, what)
+                if tuple(t.shape) != shape or not t.is_contiguous():
+                    raise ValueError(f"uavx: {what} must be a contiguous {list(shape)} tensor, got {tuple(t.shape)}")
+        for i, p in enumerate(self._params):
+            self._pptrs[i] = p.data_ptr()
+        rc = self._lib.uavx_action_grad(self.critic._h, mask, self._pptrs, state.data_ptr(), rows, s_stride,
+                                        action.data_ptr(), a_stride, q.data_ptr(), j.data_ptr(), _stream(dev))
+        _actor_lib.check_critic(rc, "uavx_action_grad")
+        return q, j
+
+    def __call__(self, state, action, towers=None):
+        """What the module's forward returns, differentiable in `action` only: (q1, q2), each [B, 1], for a twin critic
+        (one of them alone under towers=1 or 2), q [B, 1] for DDPG."""
+        mask = self._mask(towers)
+        qs = _ActionGradFn.apply(action, self, state, mask)
+        return qs if len(qs) == 2 else qs[0]
+
+    def close(self):
+        if self._owned is not None:
+            self._owned.close()
+            self._owned = None
+
+
+_ACTOR_KINDS = ((GaussianPolicy, _actor_lib.SAC), (TD3Actor, _actor_lib.TD3), (DDPGActor, _actor_lib.DDPG))
+
+
+class FusedActorLoss:
+    """The learners' actor-loss block, `zero_grad(); loss.backward()` of
+        SAC   (alpha * log_pi - min(Q1, Q2)(s, pi(s))).mean()      (model.py:88-99, sac.py:70-78)
+        TD3   -Q1(s, actor(s)).mean()                              (td3.py:144)
+        DDPG  -Q(s, actor(s)).mean()                               (ddpg.py:77-79)
+    with the critic towers in one HIP launch (FusedActionGrad) and the actor's own forward and backward torch autograd on
+    the live module; the optimiser step stays the caller's (FusedAdam or torch):
+
+        aloss = FusedActorLoss(actor, critic)     # the learner is told from the pair, as FusedTarget does
+        loss, log_pi = aloss.backward(s, alpha=alpha, generator=g)      # SAC; TD3 / DDPG: loss = aloss.backward(s)
+        actor_optim.step()
+
+    actor: the live GaussianPolicy / TD3Actor / DDPGActor.  critic: a TwinQ / TD3TwinQ / DDPGCritic, an f32 FusedCritic or
+    a FusedActionGrad."""
+
+    def __init__(self, actor, critic):
+        kind = next((k for cls, k in _ACTOR_KINDS if isinstance(actor, cls)), None)
+        if kind is None:
+            raise TypeError(f"uavx: FusedActorLoss takes a GaussianPolicy, TD3Actor or DDPGActor, not {type(actor).__name__}")
+        self._owned = None
+        if not isinstance(critic, FusedActionGrad):
+            critic = self._owned = FusedActionGrad(critic)
+        if critic.kind != kind:
+            raise TypeError(f"uavx: FusedActorLoss pairs a {_KIND_NAMES[kind]} actor ({type(actor).__name__}) with a "
+                            f"{_KIND_NAMES[critic.kind]} critic ({type(critic.module).__name__})")
+        params = list(actor.parameters())
+        for p in params:
+            if p.device != critic.device or p.dtype != torch.float32:
+                raise ValueError(f"uavx: FusedActorLoss needs the actor in float32 on the critic's device {critic.device}, "
+                                 f"a parameter is {p.dtype} on {p.device}")
+        self.actor, self.critic, self.kind, self.device = actor, critic, kind, critic.device
+        self._params = params
+
+    @property
+    def learner(self):
+        return _KIND_NAMES[self.kind].lower()
+
+    def backward(self, state, alpha=None, noise=None, generator=None):
+        """Sets every actor parameter's .grad to the gradient of the actor loss on `state` [B, 10] (cleared first, not
+        accumulated) and returns the loss as a 0-d device tensor; SAC returns (loss, log_pi.detach() [B, 1]) so that the
+        alpha update (sac.py:82) needs no second forward.  SAC: alpha is a float or a device tensor; eps is `noise`
+        ([B, 2]) or torch.randn((B, 2), generator=generator)."""
+        dev = self.device
+        rows, _ = _rows2(state, self.critic.critic.obs_dim, dev, "state")
+        if rows < 1 or rows > _actor_lib.ACTION_GRAD_MAX_ROWS:
+            raise ValueError(f"uavx: FusedActorLoss takes 1..{_actor_lib.ACTION_GRAD_MAX_ROWS} rows, got {rows}")
+        if self.kind == _actor_lib.SAC:
+            if alpha is None:
+                raise ValueError("uavx: a SAC actor loss needs alpha (a float or a device tensor)")
+            if torch.is_tensor(alpha):
+                _check_f32(alpha, dev, "alpha")
+            if noise is None:
+                noise = torch.randn((rows, 2), generator=generator, device=dev, dtype=torch.float32)
+            else:
+                _check_f32(noise, dev, "noise")
+                if tuple(noise.shape) != (rows, 2):
+                    raise ValueError(f"uavx: noise must be [{rows}, 2], got {tuple(noise.shape)}")
+        for p in self._params:
+            p.grad = None
+        with torch.enable_grad():
+            if self.kind == _actor_lib.SAC:
+                mean, log_std = self.actor(state)
+                std = log_std.exp()
+                normal = torch.distributions.Normal(mean, std, validate_args=False)   # validation would synchronise
+                x_t = mean + std * noise                                               # normal.rsample()
+                y_t = torch.tanh(x_t)                                                  # action_scale 1, action_bias 0
+                log_prob = normal.log_prob(x_t)
+                log_prob = log_prob - torch.log(1.0 * (1 - y_t.pow(2)) + 1e-6)
+                log_pi = log_prob.sum(1, keepdim=True)
+                q1, q2 = self.critic(state, y_t)
+                loss = ((alpha * log_pi) - torch.min(q1, q2)).mean()
+            elif self.kind == _actor_lib.TD3:
+                loss = -self.critic(state, self.actor(state), towers=1).mean()
+            else:
+                loss = -self.critic(state, self.actor(state)).mean()
+            loss.backward()
+        if self.kind == _actor_lib.SAC:
+            return loss.detach(), log_pi.detach()
+        return loss.detach()
+
+    def close(self):
+        """Releases the FusedActionGrad this block built (one passed in stays open)."""
         if self._owned is not None:
             self._owned.close()
             self._owned = None
