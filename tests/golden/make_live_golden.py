@@ -2,7 +2,8 @@
 """Records the REFERENCE env's side of tests/test_reference_live.py into tests/golden/live_*.npz.
 
 Run where the reference checkout is importable (see ref_loader.py):
-    python tests/golden/make_live_golden.py
+    python tests/golden/make_live_golden.py              (everything)
+    python tests/golden/make_live_golden.py thresholds   (live_thresholds.npz alone; likewise signed_zero)
 Each scenario of the three live cross-checks (seeds, agent counts, the actions fed, evaluate flags) is driven through the
 reference exactly as the tests drive the oracle, and what the tests compare is stored: the commands, the reference's
 observations after every reset, and per step its dones, positions, velocities, previous distances, flags, counters,
@@ -156,12 +157,85 @@ def make_signed_zero(MUW):
     save("live_signed_zero", rows, dict(kind="live_signed_zero", cases=16))
 
 
+# the reference's verdict at the step thresholds: one single-env world per class member of tests/threshold_layouts.py
+THR_AGENTS = (2, 3)
+THR_COMMANDS = ("f64", "f32")
+
+
+def thr_groups():
+    """(key, kind, args) of every group of live_thresholds.npz (tests/test_threshold_layouts_host.py imports this)."""
+    sys.path.insert(0, os.path.dirname(HERE))
+    import threshold_layouts as tl
+    out = [(f"muw_n{n}_{w}_{c}", "muw", (n, w, c)) for n in THR_AGENTS for w in tl.WORLDS for c in THR_COMMANDS]
+    out += [(f"uw_{b}_{c}_{'fresh' if f else 'later'}", "uw", (b, c, f)) for b in tl.UW_BOXES for c in THR_COMMANDS
+            for f in (False, True)]
+    return tl, out
+
+
+def make_thresholds(MUW, UW):
+    """Pokes the crafted state of every class member (section 0 of the batch) into a fresh reference world and records two
+    steps with evaluate=False and, from the same state again, one with evaluate=True."""
+    tl, groups = thr_groups()
+    data = {}
+    for key, kind, args in groups:
+        rows = {}
+        if kind == "muw":
+            n, world, cmd = args
+            b = tl.make_threshold_batch(n, world, cmd)
+            envs = np.flatnonzero((b["section"] == 0) & ~b["filler"])
+            for e in envs:
+                for ev in (False, True):
+                    np.random.seed(500 + int(e))
+                    env = MUW(num_agents=n, **tl.WORLDS[world])
+                    env.reset()
+                    for i, a in enumerate(env.agent_list):
+                        a.location, a.target_location = b["loc"][e, i].copy(), b["tgt"][e, i].copy()
+                        a.velocity, a.velocity_prev = b["vel"][e, i].copy(), b["vel"][e, i].copy()
+                        a.init_distance, a.prev_distance = b["init_d"][e, i], b["prev_d"][e, i]
+                    act = b["act32"][e] if cmd == "f32" else b["act"][e]
+                    for t in range(1 if ev else 2):
+                        _, rew, done, _ = env.step([act[i].copy() for i in range(n)], evaluate=ev)
+                        tag = "eval" if ev else f"step{t + 1}"
+                        record(rows, **{f"{tag}_{k}": v for k, v in dict(snap(env), done=np.array(done, np.uint8),
+                                                                          rew=np.array([float(r) for r in rew])).items()})
+            rows["env"] = envs
+            for k in ("loc", "vel", "tgt", "init_d", "prev_d", "act"):
+                rows["in_" + k] = b[k][envs]
+        else:
+            box, cmd, fresh = args
+            b = tl.make_uw_batch(box, cmd, fresh)
+            for e in range(b["loc"].shape[0]):
+                np.random.seed(600 + e)
+                env = UW(**tl.UW_BOXES[box])
+                env.reset()
+                env._agent_location, env._target_location = b["loc"][e].copy(), b["tgt"][e].copy()
+                vel = b["vel"][e].astype(np.float32) if fresh else b["vel"][e].copy()
+                env._agent_speed = env._agent_speed_prev = vel
+                env._init_target_distance, env._prev_distance = b["init_d"][e], b["prev_d"][e]
+                act = b["act32"][e] if cmd == "f32" else b["act"][e]
+                for t in range(2):
+                    obs, rew, done, info = env.step(act.copy())
+                    record(rows, **{f"step{t + 1}_{k}": v for k, v in dict(
+                        done=np.uint8(bool(done)), rew=np.float64(rew), distance=np.float64(info["distance"]),
+                        obs=np.asarray(obs, np.float64), loc=np.asarray(env._agent_location, np.float64),
+                        vel=np.asarray(env._agent_speed, np.float64)).items()})
+            for k in ("loc", "vel", "tgt", "init_d", "prev_d", "act"):
+                rows["in_" + k] = b[k]
+        for k, v in rows.items():
+            data[f"{key}__{k}"] = np.stack(v) if isinstance(v, list) else v
+    save("live_thresholds", data, dict(kind="live_thresholds", groups=[g[0] for g in groups]))
+
+
 if __name__ == "__main__":
     MUW, UW, _ = ref_loader.load()
     if sys.argv[1:] == ["signed_zero"]:
         make_signed_zero(MUW)
         sys.exit(0)
+    if sys.argv[1:] == ["thresholds"]:
+        make_thresholds(MUW, UW)
+        sys.exit(0)
     make_muw(MUW)
     make_uw(UW)
     make_f64(MUW)
     make_signed_zero(MUW)
+    make_thresholds(MUW, UW)
