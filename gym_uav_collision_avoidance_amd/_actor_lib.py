@@ -1,6 +1,7 @@
 """ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h,
-include/uavx_optim.h, include/uavx_replay.h, include/uavx_action_grad.h), the fused actor-inference, critic, TD-target,
-critic-gradient, optimiser-step, replay-sampling and critic action-gradient kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+include/uavx_optim.h, include/uavx_replay.h, include/uavx_action_grad.h, include/uavx_policy_grad.h), the fused
+actor-inference, critic, TD-target, critic-gradient, optimiser-step, replay-sampling, critic action-gradient and actor
+forward / backward kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
 that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
 missing library or device raises."""
 import ctypes
@@ -16,6 +17,7 @@ GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic_grad.
 OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_optim.h")
 REPLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_replay.h")
 ACTION_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_action_grad.h")
+POLICY_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_policy_grad.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -50,6 +52,11 @@ REPLAY_SINGLE_ROWS = 1024   # UAVX_REPLAY_SINGLE_ROWS: up to here one launch and
 ACTION_GRAD_SYMBOLS = ("uavx_action_grad_version", "uavx_action_grad")
 ACTION_GRAD_ABI_VERSION = 1
 ACTION_GRAD_MAX_ROWS = 262144   # UAVX_ACTION_GRAD_MAX_ROWS
+# every symbol include/uavx_policy_grad.h declares
+POLICY_GRAD_SYMBOLS = ("uavx_policy_grad_version", "uavx_policy_grad_workspace_bytes", "uavx_policy_grad_forward",
+                       "uavx_policy_grad_backward")
+POLICY_GRAD_ABI_VERSION = 1
+POLICY_GRAD_MAX_ROWS = 262144   # UAVX_POLICY_GRAD_MAX_ROWS
 
 _lib_handle = None
 
@@ -63,11 +70,12 @@ class ReplayRing(ctypes.Structure):
 def _sources():
     import glob
     return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER])
+            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER,
+               POLICY_GRAD_HEADER])
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the six headers of include/, plus
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the seven headers of include/, plus
     the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
     return _native.source_hash(CSRC, _sources())
 
@@ -137,6 +145,13 @@ def load():
         raise RuntimeError(f"{LIB_PATH} speaks action-gradient ABI version {L.uavx_action_grad_version()}, this package "
                            f"binds {ACTION_GRAD_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
     L.uavx_action_grad.argtypes = [vp, i32, pvp, vp, i64, i64, vp, i64, vp, vp, vp]
+    L.uavx_policy_grad_version.restype = i32
+    if L.uavx_policy_grad_version() != POLICY_GRAD_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks policy-gradient ABI version {L.uavx_policy_grad_version()}, this package "
+                           f"binds {POLICY_GRAD_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_policy_grad_workspace_bytes.argtypes = [i32, i32, i32, i64, pi64]
+    L.uavx_policy_grad_forward.argtypes = [i32, i32, i32, pvp, vp, i64, i64, vp, vp, vp, vp, i64, vp]
+    L.uavx_policy_grad_backward.argtypes = [i32, i32, i32, pvp, vp, i64, i64, vp, vp, i64, f32, vp, pvp, vp, vp, vp, i64, vp]
     _lib_handle = L
     return L
 
