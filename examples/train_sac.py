@@ -1,0 +1,57 @@
+#!/usr/bin/env python3
+"""A closed SAC training loop with nothing leaving the GPU between reports: UAVVectorEnv builds the worlds, DeviceReplay
+is the ring the step launch writes into, FusedSAC acts from its packed policy and replays its captured update
+(test_sac_multi.py:62-119 in batch form).  The host reads one row of the loss ring and the episode statistics per report.
+
+    python examples/train_sac.py [--envs 1024] [--agents 4] [--steps 2000] [--batch 256] [--updates-per-step 1]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gym_uav_collision_avoidance_amd import UAVVectorEnv
+from gym_uav_collision_avoidance_amd.learners import FusedSAC
+from gym_uav_collision_avoidance_amd.replay import DeviceReplay
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=1024)
+ap.add_argument("--agents", type=int, default=4)
+ap.add_argument("--steps", type=int, default=2000)
+ap.add_argument("--horizon", type=int, default=256)
+ap.add_argument("--batch", type=int, default=256)
+ap.add_argument("--start-steps", type=int, default=16, help="steps collected before the first update")
+ap.add_argument("--updates-per-step", type=int, default=1)
+ap.add_argument("--report", type=int, default=500)
+ap.add_argument("--checkpoint", type=str, default=None, help="directory to write weights.chpt into at the end")
+args = ap.parse_args()
+
+dev = torch.device("cuda", 0)
+venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=0)
+mem = DeviceReplay(venv.env, horizon=args.horizon)
+mem.begin(venv.reset())
+gen = torch.Generator(device=dev).manual_seed(0)
+agent = FusedSAC(device=dev, generator=gen, memory=mem)
+
+t0 = time.perf_counter()
+for t in range(args.steps):
+    agent.select_action(mem.state, evaluate=False, out=mem.action_slot())      # the policy writes the ring's action slot
+    mem.step(polar=True, auto_reset="agent0_done", step_cap=1500, track_returns=True)
+    if t + 1 == args.start_steps:
+        agent.capture(args.batch)                                              # sampling + the whole update, one graph
+    if t + 1 >= args.start_steps:
+        agent.run(args.updates_per_step)
+    if (t + 1) % args.report == 0 and agent.updates:
+        q1, q2, pi, al, alpha = agent.losses(last=1)[0, :5]                    # the one host read
+        print(f"step {t + 1}: {agent.updates} updates, critic {q1:.4f} {q2:.4f} policy {pi:.4f} alpha_loss {al:.4f} "
+              f"alpha {alpha:.4f}, {(t + 1) * args.envs / (time.perf_counter() - t0):,.0f} env steps/s")
+torch.cuda.synchronize()
+st = venv.episode_stats()
+print(f"{int(st['episodes'].sum())} episodes ended: {int(st['reach'].sum())} reached the goal, {int(st['coll'].sum())} collided")
+if args.checkpoint:
+    print("wrote", agent.save_checkpoint(args.checkpoint))
+agent.close()
+venv.close()

@@ -1,7 +1,7 @@
 """ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h,
-include/uavx_optim.h, include/uavx_replay.h, include/uavx_action_grad.h, include/uavx_policy_grad.h), the fused
-actor-inference, critic, TD-target, critic-gradient, optimiser-step, replay-sampling, critic action-gradient and actor
-forward / backward kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+include/uavx_optim.h, include/uavx_replay.h, include/uavx_action_grad.h, include/uavx_policy_grad.h,
+include/uavx_learner.h), the fused actor-inference, critic, TD-target, critic-gradient, optimiser-step, replay-sampling,
+critic action-gradient, actor forward / backward and learner-tail kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
 that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
 missing library or device raises."""
 import ctypes
@@ -18,6 +18,7 @@ OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_optim.h")
 REPLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_replay.h")
 ACTION_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_action_grad.h")
 POLICY_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_policy_grad.h")
+LEARNER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_learner.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -57,6 +58,10 @@ POLICY_GRAD_SYMBOLS = ("uavx_policy_grad_version", "uavx_policy_grad_workspace_b
                        "uavx_policy_grad_backward")
 POLICY_GRAD_ABI_VERSION = 1
 POLICY_GRAD_MAX_ROWS = 262144   # UAVX_POLICY_GRAD_MAX_ROWS
+# every symbol include/uavx_learner.h declares
+LEARNER_SYMBOLS = ("uavx_learner_version", "uavx_learner_tail")
+LEARNER_ABI_VERSION = 1
+LEARNER_LOG_COLUMNS = 8         # UAVX_LEARNER_LOG_COLUMNS
 
 _lib_handle = None
 
@@ -71,11 +76,11 @@ def _sources():
     import glob
     return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
             + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER,
-               POLICY_GRAD_HEADER])
+               POLICY_GRAD_HEADER, LEARNER_HEADER])
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the seven headers of include/, plus
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the eight headers of include/, plus
     the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
     return _native.source_hash(CSRC, _sources())
 
@@ -152,6 +157,11 @@ def load():
     L.uavx_policy_grad_workspace_bytes.argtypes = [i32, i32, i32, i64, pi64]
     L.uavx_policy_grad_forward.argtypes = [i32, i32, i32, pvp, vp, i64, i64, vp, vp, vp, vp, i64, vp]
     L.uavx_policy_grad_backward.argtypes = [i32, i32, i32, pvp, vp, i64, i64, vp, vp, i64, f32, vp, pvp, vp, vp, vp, i64, vp]
+    L.uavx_learner_version.restype = i32
+    if L.uavx_learner_version() != LEARNER_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks learner ABI version {L.uavx_learner_version()}, this package binds "
+                           f"{LEARNER_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_learner_tail.argtypes = [i32, pvp, vp, f32, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, i64, vp, i32, vp]
     _lib_handle = L
     return L
 

@@ -175,6 +175,14 @@ class FusedAdam:
     def param_groups(self):
         return self.optimizer.param_groups
 
+    def hyper(self, group=0):
+        """(lr, beta1, beta2, eps) of a param group as the next step would read them (raises on what is not implemented)."""
+        return self._hyper(self.optimizer.param_groups[group])
+
+    def step_pointer(self, group=0):
+        """Device address of the int64 step count of a param group, for a kernel that takes the group's step itself."""
+        return self._step_ptr + 8 * group
+
     def zero_grad(self, set_to_none=True):
         self.optimizer.zero_grad(set_to_none=set_to_none)
 

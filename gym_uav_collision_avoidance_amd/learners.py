@@ -1,0 +1,634 @@
+"""FusedSAC, FusedTD3, FusedDDPG: the reference's three learners (pytorch_sac_temp/sac.py, pytorch_td3_temp/td3.py,
+pytorch_ddpg_temp/ddpg.py) with every step of update_parameters as HIP launches of libuavx_actor.so:
+
+    sample   FusedReplaySampler on a DeviceReplay                          (§16)
+    target   FusedTarget: next action, target critic, y                    (§13)
+    critic   FusedCriticLoss into .grad, FusedAdam step                    (§14, §15)
+    actor    FusedPolicyGrad into .grad, FusedAdam step, soft updates      (§17, §18, §15)
+    tail     SAC's alpha step and the loss record (include/uavx_learner.h) (§19)
+
+    agent = FusedSAC(memory=mem)                       # constructor keywords and attribute names of the reference's SAC
+    agent.update_parameters(mem, 256)                  # one update, eager; returns nothing, syncs nothing
+    agent.capture(256); agent.run(1000)                # the same update as a captured graph, replayed
+    agent.losses(last=10)                              # the ONE host read: [n, 8] rows of the loss ring, in update order
+    a = agent.select_action(mem.state)                 # FusedActor.act on the live actor
+
+A row of the loss ring holds critic_loss_1, critic_loss_2 (0 for DDPG), actor_loss (0 in an update without an actor
+step), alpha_loss, alpha, actor_updated, 0, 0: what the reference's update_parameters returns through .item().
+
+One deliberate difference from the reference: sac.py:29 reads its target_entropy from an uninitialised tensor
+(torch.Tensor(n_actions) with an int); FusedSAC takes target_entropy=None -> -float(n_actions), the value the comment at
+sac.py:28 intends.  Everything else follows the reference, its quirks included: SAC's update 0 uses alpha = `alpah` (2)
+and later updates exp(log_alpha); TD3 steps the actor and both targets only when updates % policy_freq == 0.
+There is NO fallback: anything the kernels do not implement raises before a launch."""
+import ctypes
+import math
+import os
+
+import torch
+
+from . import _actor_lib, policy
+from .fused_actor import FusedActor
+from .fused_critic import FusedCritic, FusedCriticLoss, FusedTarget
+from .fused_optim import FusedAdam, soft_update
+from .fused_policy_grad import FusedPolicyGrad
+from .fused_replay import FusedReplaySampler
+from .replay import DeviceReplay
+
+LOG_COLUMNS = _actor_lib.LEARNER_LOG_COLUMNS
+COLUMNS = ("critic_loss_1", "critic_loss_2", "actor_loss", "alpha_loss", "alpha", "actor_updated")
+
+
+def _stream(device):
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def _check_f32(t, device, what):
+    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != device:
+        raise TypeError(f"uavx: {what} must be a float32 tensor on {device}, got {getattr(t, 'dtype', type(t))} on "
+                        f"{getattr(t, 'device', 'host')}")
+
+
+def _cpu(x):
+    """A state dict (module's or optimiser's) with every tensor detached and on the CPU."""
+    if torch.is_tensor(x):
+        return x.detach().cpu()
+    if isinstance(x, dict):
+        return {k: _cpu(v) for k, v in x.items()}
+    if isinstance(x, (list, tuple)):
+        return type(x)(_cpu(v) for v in x)
+    return x
+
+
+def ddpg_init(net, init_w):
+    """pytorch_ddpg_temp/model.py's init_weights on a DDPGActor / DDPGCritic: `input` and `fc1` weights from
+    U(+-1/sqrt(size[0])), size[0] being the layer's OUT features (fanin_init's quirk, model.py:62-65), `fc2`'s from
+    U(+-init_w) (5e-4 for the actor, 5e-5 for the critic); the biases keep nn.Linear's default, as there."""
+    with torch.no_grad():
+        for lin in (net.input, net.fc1):
+            b = 1.0 / math.sqrt(lin.weight.shape[0])
+            lin.weight.uniform_(-b, b)
+        net.fc2.weight.uniform_(-init_w, init_w)
+    return net
+
+
+def _copy_params(target, source):
+    with torch.no_grad():
+        for t, s in zip(target.parameters(), source.parameters()):
+            t.copy_(s)
+
+
+def _amend(path, entries):
+    """Adds / replaces entries of a checkpoint file one of policy.py's savers wrote (tensors stored on the CPU)."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    ck.update(entries)
+    torch.save(ck, path)
+
+
+class _FusedLearner:
+    """What the three learners share: the loss ring, the tail launch, sampling, capture / run and the batch checks."""
+    kind = None
+    _noises = 0          # [B, 2] standard-normal tensors one update consumes
+
+    def _setup(self, device, generator, log_capacity, memory):
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise ValueError(f"uavx: the learners need a GPU (cuda:N), got {self.device}: there is no CPU path")
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if generator is not None and generator.device != self.device:
+            raise ValueError(f"uavx: generator is on {generator.device}, the learner on {self.device}")
+        log_capacity = int(log_capacity)
+        if log_capacity < 1:
+            raise ValueError(f"uavx: log_capacity must be >= 1, got {log_capacity}")
+        self.generator, self.log_capacity = generator, log_capacity
+        self._lib = _actor_lib.load()
+        # the loss ring and, behind it in the same allocation, the int64 count the tail launch advances: one copy reads both
+        self._ring = torch.zeros(log_capacity * LOG_COLUMNS + 2, dtype=torch.float32, device=self.device)
+        self._log = self._ring[:-2].view(log_capacity, LOG_COLUMNS)
+        self._updates = self._ring[-2:].view(torch.int64)
+        self.updates = 0                  # the host's count of updates enqueued: what `updates=None` stands for
+        self._losses_in = (ctypes.c_void_p * 3)()
+        self._sampler = self._batch = self._y = None
+        self._graphs = None
+        self.memory = None
+        if memory is not None:
+            self.attach(memory)
+
+    # ---- pieces the subclasses name -----------------------------------------------------------------------------------
+    def _pieces(self):
+        """(FusedCriticLoss, FusedPolicyGrad): what reserve() sizes."""
+        return self._closs, self._pgrad
+
+    def _variants(self):
+        """The `full` flags an update can run with: one graph is captured for each."""
+        return (True,)
+
+    def _full(self, updates):
+        return True
+
+    def _update(self, s, a, r, s2, mask, noise, full):
+        raise NotImplementedError
+
+    # ---- the tail -----------------------------------------------------------------------------------------------------
+    def _tail(self, critic_loss, actor_loss, sac=None):
+        """One launch: the loss row, the update count and (sac = (log_pi_mean, hyper) with automatic entropy tuning)
+        the alpha step.  critic_loss: what FusedCriticLoss.backward returned (0-d device views, two for a twin critic);
+        actor_loss: FusedPolicyGrad's, or None in an update without an actor step."""
+        li = self._losses_in
+        twin = isinstance(critic_loss, tuple)
+        li[0] = (critic_loss[0] if twin else critic_loss).data_ptr()
+        li[1] = critic_loss[1].data_ptr() if twin else None
+        li[2] = None if actor_loss is None else actor_loss.data_ptr()
+        alpha = getattr(self, "_alpha", None)
+        if sac is None:
+            args = (None, 0.0, None, None, None, None, 0.0, 0.0, 0.0, 0.0)
+        else:
+            lpm, (lr, b1, b2, eps) = sac
+            st = self.alpha_optim.state[self.log_alpha]
+            args = (lpm.data_ptr(), self.target_entropy, self.log_alpha.data_ptr(), st["exp_avg"].data_ptr(),
+                    st["exp_avg_sq"].data_ptr(), self._alpha_adam.step_pointer(), lr, b1, b2, eps)
+        with torch.cuda.device(self.device):
+            rc = self._lib.uavx_learner_tail(self.kind, li, *args, None if alpha is None else alpha.data_ptr(),
+                                             self._log.data_ptr(), self.log_capacity, self._updates.data_ptr(),
+                                             int(actor_loss is not None), _stream(self.device))
+        _actor_lib.check(rc, "uavx_learner_tail")
+
+    # ---- batches ------------------------------------------------------------------------------------------------------
+    def _check_batch(self, s, a, r, s2, mask, noise):
+        dev = self.device
+        for t, cols, what in ((s, 10, "state"), (a, 2, "action"), (s2, 10, "next_state")):
+            _check_f32(t, dev, what)
+            if t.dim() != 2 or t.shape[1] != cols:
+                raise ValueError(f"uavx: {what} must be [B, {cols}], got {tuple(t.shape)}")
+        rows = s.shape[0]
+        if rows < 1 or a.shape[0] != rows or s2.shape[0] != rows:
+            raise ValueError(f"uavx: state, action and next_state must have the same B >= 1 rows, got {rows}, "
+                             f"{a.shape[0]}, {s2.shape[0]}")
+        for t, what in ((r, "reward"), (mask, "mask")):
+            _check_f32(t, dev, what)
+            if tuple(t.shape) not in ((rows,), (rows, 1)):
+                raise ValueError(f"uavx: {what} must be [{rows}] or [{rows}, 1], got {tuple(t.shape)}")
+        if self._noises == 0:
+            if noise is not None:
+                raise ValueError(f"uavx: {type(self).__name__} draws no noise in its update")
+            return rows, ()
+        if noise is None:
+            return rows, (None,) * self._noises
+        noise = (noise,) if torch.is_tensor(noise) else tuple(noise)
+        if len(noise) != self._noises:
+            raise ValueError(f"uavx: {type(self).__name__}.update_batch takes {self._noises} noise tensor(s) "
+                             f"([B, 2] standard normal), got {len(noise)}")
+        for n in noise:
+            _check_f32(n, dev, "noise")
+            if tuple(n.shape) != (rows, 2) or not n.is_contiguous():
+                raise ValueError(f"uavx: noise must be a contiguous [{rows}, 2] tensor, got {tuple(n.shape)}")
+        return rows, noise
+
+    def _target_out(self, rows):
+        """y [rows, 1]: the reserved buffer, or a new one outside a capture."""
+        if self._y is not None and self._y.shape[0] >= rows:
+            return self._y[:rows]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"uavx: the buffers for {rows} rows must exist before a graph capture: call reserve({rows}) "
+                               f"first")
+        return torch.empty((rows, 1), dtype=torch.float32, device=self.device)
+
+    def reserve(self, rows):
+        """Sizes every workspace and buffer an update of `rows` rows needs (a graph capture cannot allocate them)."""
+        rows = int(rows)
+        closs, pgrad = self._pieces()
+        closs.reserve(rows)
+        pgrad.reserve(rows)
+        if self._y is None or self._y.shape[0] < rows:
+            self._y = torch.empty((rows, 1), dtype=torch.float32, device=self.device)
+        if self._sampler is not None:
+            self._sampler.reserve(rows)
+        return self
+
+    def update_batch(self, s, a, r, s2, mask, noise=None, updates=None):
+        """One update of the reference's update_parameters on the given device tensors: state [B, 10], action [B, 2],
+        reward and mask [B] or [B, 1], next_state [B, 10].  noise: the standard-normal draws of the update as [B, 2] device
+        tensors -- SAC (target's, policy's), TD3 the target's, DDPG none; None draws them from the learner's generator.
+        updates: the reference's `updates` argument (TD3's policy_freq, SAC's target_update_interval); None = the number of
+        updates run so far.  Returns nothing: the numbers are in the loss ring (losses())."""
+        rows, noise = self._check_batch(s, a, r, s2, mask, noise)
+        u = self.updates if updates is None else int(updates)
+        self._update(s, a, r, s2, mask, noise, self._full(u))
+        self.updates += 1
+
+    def attach(self, memory):
+        """The DeviceReplay that update_parameters(None, ...) and capture() sample from."""
+        if not isinstance(memory, DeviceReplay):
+            raise TypeError(f"uavx: the learners sample from a DeviceReplay, not {type(memory).__name__}")
+        if self.memory is not memory:
+            self.memory, self._sampler = memory, FusedReplaySampler(memory)
+            self._graphs = None
+        return self
+
+    def update_parameters(self, memory, batch_size, updates=None):
+        """One update, eager, with no host synchronisation.  memory: a DeviceReplay (sampled through FusedReplaySampler
+        with the learner's generator), None for the attached one, or an explicit (state, action, reward, next_state, mask)
+        tuple of device tensors.  Returns nothing: the numbers are in the loss ring."""
+        if isinstance(memory, (tuple, list)):
+            if len(memory) != 5:
+                raise ValueError(f"uavx: an explicit batch is (state, action, reward, next_state, mask), got {len(memory)} "
+                                 f"entries")
+            s, a, r, s2, mask = memory
+            if s.shape[0] != int(batch_size):
+                raise ValueError(f"uavx: the batch has {s.shape[0]} rows, batch_size is {batch_size}")
+        else:
+            if memory is not None:
+                self.attach(memory)
+            if self._sampler is None:
+                raise ValueError("uavx: update_parameters needs a DeviceReplay (or attach() one first)")
+            s, a, r, s2, mask = self._sampler.sample(int(batch_size), generator=self.generator)
+        self.update_batch(s, a, r, s2, mask, updates=updates)
+
+    # ---- capture / run ------------------------------------------------------------------------------------------------
+    def _throwaway(self):
+        """A learner of the same class and shapes whose one update loads every kernel before a capture."""
+        raise NotImplementedError
+
+    def capture(self, batch_size, memory=None):
+        """Captures one update of `batch_size` rows, sampling included, as a torch.cuda.graph (TD3: two, critic-only and
+        full; SAC with target_update_interval > 1: two, with and without the target update).  The graph samples from the
+        attached DeviceReplay (`memory` attaches one) with the learner's generator and reads the ring's fill through a
+        device count that run() refreshes."""
+        rows = int(batch_size)
+        if rows < 1:
+            raise ValueError(f"uavx: capture needs batch_size >= 1, got {batch_size}")
+        if memory is not None:
+            self.attach(memory)
+        if self._sampler is None:
+            raise ValueError("uavx: capture needs a DeviceReplay: pass memory= here or to the constructor")
+        dev, gen, sampler = self.device, self.generator, self._sampler
+        self.reserve(rows)
+        # everything a first call creates lazily happens here, on a side stream: the kernels are loaded by a throw-away
+        # learner's update, the sampler's uniforms by a sample whose draw is taken back
+        state = None if gen is None else gen.get_state()
+        side = torch.cuda.Stream(dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.random.fork_rng(devices=[dev]), torch.cuda.stream(side):
+            batch = sampler.sample(rows, generator=gen)
+            warm = self._throwaway()
+            for full in self._variants():
+                warm._update(*batch, (None,) * self._noises, full)
+            torch.cuda.synchronize(dev)
+            warm.close()
+        torch.cuda.current_stream(dev).wait_stream(side)
+        if gen is not None:
+            gen.set_state(state)
+        self._batch = tuple(torch.empty_like(t) for t in batch)
+        graphs = {}
+        for full in self._variants():
+            g = torch.cuda.CUDAGraph()
+            if gen is not None:
+                g.register_generator_state(gen)
+            with torch.cuda.graph(g):
+                b = sampler.sample(rows, generator=gen, out=self._batch, device_count=True)
+                self._update(*b, (None,) * self._noises, full)
+            graphs[full] = g
+        self._graphs = graphs
+        return self
+
+    def run(self, n=1):
+        """Replays the captured update n times (no host synchronisation)."""
+        if self._graphs is None:
+            raise RuntimeError("uavx: run() needs capture(batch_size) first")
+        for _ in range(int(n)):
+            self._sampler.push_count()
+            self._graphs[self._full(self.updates)].replay()
+            self._ran(self._full(self.updates))
+            self.updates += 1
+
+    def _ran(self, full):
+        """Host bookkeeping behind a replay."""
+
+    # ---- reading back -------------------------------------------------------------------------------------------------
+    def losses(self, last=None):
+        """The last `last` rows of the loss ring (None: all it still holds) in update order, as a numpy [n, 8] array: the
+        one host read (a single device-to-host copy of the ring and its count; it synchronises)."""
+        ring = self._ring.cpu()
+        u, log = int(ring[-2:].view(torch.int64)), ring[:-2].view(self.log_capacity, LOG_COLUMNS).numpy()
+        n = min(u, self.log_capacity) if last is None else min(int(last), u, self.log_capacity)
+        return log[[(u - n + i) % self.log_capacity for i in range(n)]].reshape(n, LOG_COLUMNS)
+
+    def _set_updates(self, u):
+        self.updates = int(u)
+        self._updates.fill_(self.updates)
+
+    def refresh(self):
+        """Re-packs every snapshot the kernels read: call it after writing into the modules by hand (load_state_dict);
+        load_checkpoint does it itself."""
+        for h in self._packed():
+            h.refresh()
+        return self
+
+    def close(self):
+        for x in self._handles():
+            x.close()
+
+
+class FusedSAC(_FusedLearner):
+    """sac.py's SAC: policy, critic, critic_target, critic_optim, policy_optim, log_alpha, alpha_optim under the
+    reference's names; `alpha` is the 1-element device tensor every kernel reads."""
+    kind = _actor_lib.SAC
+    _noises = 2
+
+    def __init__(self, n_states=10, n_actions=2, lr=3e-4, tau=5e-3, gamma=0.99, alpah=2, target_update_interval=1,
+                 automatic_entropy_tuning=True, target_entropy=None, device="cuda", generator=None, log_capacity=1024,
+                 memory=None, hidden=256):
+        self.lr, self.tau, self.gamma = lr, tau, gamma
+        self.target_update_interval = int(target_update_interval)
+        if self.target_update_interval < 1:
+            raise ValueError(f"uavx: target_update_interval must be >= 1, got {target_update_interval}")
+        self.automatic_entropy_tuning = bool(automatic_entropy_tuning)
+        self._setup(device, generator, log_capacity, memory)
+        dev = self.device
+        self._dims = dict(n_states=n_states, n_actions=n_actions, hidden=hidden)
+        self.critic = policy.TwinQ(n_states, n_actions, hidden).to(dev)
+        self.critic_optim = torch.optim.Adam(self.critic.parameters(), lr=lr)
+        self.critic_target = policy.TwinQ(n_states, n_actions, hidden).to(dev)
+        _copy_params(self.critic_target, self.critic)                                  # hard_update, sac.py:26
+        self._alpha = torch.full((1,), float(alpah), dtype=torch.float32, device=dev)  # update 0 runs with `alpah`
+        self.target_entropy = -float(n_actions) if target_entropy is None else float(target_entropy)
+        if self.automatic_entropy_tuning:
+            self.log_alpha = torch.zeros(1, requires_grad=True, device=dev)
+            self.alpha_optim = torch.optim.Adam([self.log_alpha], lr=lr)
+            self._alpha_adam = FusedAdam(self.alpha_optim)      # keeps the state in torch's format; the tail does the step
+        self.policy = policy.GaussianPolicy(n_states, n_actions, hidden).to(dev)
+        with torch.no_grad():
+            for m in self.policy.modules():                                             # weights_init_, model.py:10-14
+                if isinstance(m, torch.nn.Linear):
+                    torch.nn.init.xavier_uniform_(m.weight, gain=1)
+                    torch.nn.init.constant_(m.bias, 0)
+        self.policy_optim = torch.optim.Adam(self.policy.parameters(), lr=lr)
+        self._build()
+
+    def _build(self):
+        # the target block reads packed snapshots of the LIVE policy (sac.py:57) and of critic_target
+        self._actor_h = FusedActor.from_module(self.policy)
+        self._target_h = FusedCritic.from_module(self.critic_target)
+        self._target = FusedTarget(self._actor_h, self._target_h, gamma=self.gamma)
+        self._closs = FusedCriticLoss(self.critic)
+        self._pgrad = FusedPolicyGrad(self.policy, self._closs.critic)
+        self._critic_adam = FusedAdam(self.critic_optim, target=self.critic_target, tau=self.tau)
+        self._policy_adam = FusedAdam(self.policy_optim)
+
+    def _handles(self):
+        return (self._pgrad, self._closs, self._target, self._actor_h, self._target_h)
+
+    def _packed(self):
+        return (self._actor_h, self._target_h)
+
+    @property
+    def alpha(self):
+        """The temperature the next update runs with: a 1-element float32 device tensor."""
+        return self._alpha
+
+    def _variants(self):
+        return (True,) if self.target_update_interval == 1 else (True, False)
+
+    def _full(self, updates):
+        return updates % self.target_update_interval == 0
+
+    def _update(self, s, a, r, s2, mask, noise, full):
+        gen = self.generator
+        y = self._target(s2, r, mask, alpha=self._alpha, generator=gen, noise=noise[0], out=self._target_out(s.shape[0]))
+        critic_loss = self._closs.backward(s, a, y)
+        # the soft update reads only the critic: it rides in the critic's step, and the packed target follows it
+        self._critic_adam.step(update_target=full, refresh=self._target_h if full else None)
+        policy_loss, _ = self._pgrad.backward(s, alpha=self._alpha, noise=noise[1], generator=gen)
+        self._policy_adam.step(refresh=self._actor_h)
+        sac = None
+        if self.automatic_entropy_tuning:
+            sac = (self._pgrad.log_pi_mean, self._alpha_adam.hyper())
+        self._tail(critic_loss, policy_loss, sac)
+
+    def _throwaway(self):
+        return FusedSAC(lr=self.lr, tau=self.tau, gamma=self.gamma, device=self.device, log_capacity=1,
+                        automatic_entropy_tuning=self.automatic_entropy_tuning, **self._dims)
+
+    def select_action(self, obs, evaluate=False, out=None):
+        """sac.py:38-44 over any batch of observations [..., 10] on the device: tanh(mean + std·eps), or tanh(mean) when
+        evaluating; one launch on the packed live policy."""
+        return self._actor_h.act(obs, evaluate=evaluate, generator=self.generator, out=out)
+
+    def save_checkpoint(self, ckpt_path, file_name=None):
+        """sac.py:101-114's file (policy.save_reference_checkpoint), plus what a bit-exact continuation needs and the
+        reference does not keep: log_alpha, its optimiser, alpha and the update count."""
+        path = os.path.join(ckpt_path, "weights.chpt" if file_name is None else file_name)
+        self._critic_adam.sync_state()
+        self._policy_adam.sync_state()
+        policy.save_reference_checkpoint(path, self.policy, self.critic, self.critic_target, self.critic_optim,
+                                         self.policy_optim)
+        extra = {"alpha": self._alpha.detach().cpu(), "updates": self.updates}
+        if self.automatic_entropy_tuning:
+            extra["log_alpha"] = self.log_alpha.detach().cpu()
+            extra["alpha_optimizer_state_dict"] = _cpu(self._alpha_adam.state_dict())
+        _amend(path, extra)
+        return path
+
+    def load_checkpoint(self, ckpt_path, file_name=None, evaluate=False):
+        path = os.path.join(ckpt_path, "weights.chpt" if file_name is None else file_name)
+        ck = torch.load(path, map_location=self.device, weights_only=True)
+        self.policy.load_state_dict(ck["policy_state_dict"])
+        self.critic.load_state_dict(ck["critic_state_dict"])
+        self.critic_target.load_state_dict(ck["critic_target_state_dict"])
+        self._critic_adam.load_state_dict(ck["critic_optimizer_state_dict"])
+        self._policy_adam.load_state_dict(ck["policy_optimizer_state_dict"])
+        if "alpha" in ck:
+            self._alpha.copy_(ck["alpha"])
+        if self.automatic_entropy_tuning and "log_alpha" in ck:
+            with torch.no_grad():
+                self.log_alpha.copy_(ck["log_alpha"])
+            self._alpha_adam.load_state_dict(ck["alpha_optimizer_state_dict"])
+        self._set_updates(ck.get("updates", 0))
+        for m in (self.policy, self.critic, self.critic_target):
+            m.eval() if evaluate else m.train()
+        self._graphs = None                 # a captured graph holds the addresses of the optimiser state it replaced
+        return self.refresh()
+
+
+class _ActorCriticLearner(_FusedLearner):
+    """TD3 and DDPG: actor, actor_target, critic, critic_target and the two optimisers."""
+
+    def _build(self, **target_kw):
+        self._actor_h = FusedActor.from_module(self.actor)          # select_action's: the live actor (_live)
+        self._stale = False
+        self._target = FusedTarget(self.actor_target, self.critic_target, gamma=self._gamma, **target_kw)
+        self._closs = FusedCriticLoss(self.critic)
+        self._pgrad = FusedPolicyGrad(self.actor, self._closs.critic)
+        self._critic_adam = FusedAdam(self.critic_optimizer)
+        self._actor_adam = FusedAdam(self.actor_optimizer, target=self.actor_target, tau=self.tau)
+
+    def _handles(self):
+        return (self._pgrad, self._closs, self._target, self._actor_h)
+
+    def _packed(self):
+        return (self._actor_h, self._target)
+
+    def _actor_and_targets(self, s):
+        """The actor update and both soft updates, the actor's first (td3.py:141-156, ddpg.py:73-83) -> the actor loss."""
+        actor_loss = self._pgrad.backward(s)
+        self._actor_adam.step(update_target=True)
+        soft_update(self.critic_target, self.critic, self.tau)
+        self._target.refresh()
+        self._stale = True
+        return actor_loss
+
+    def _ran(self, full):
+        self._stale = self._stale or full
+
+    def refresh_actor(self):
+        """Re-packs select_action's copy of the live actor now (one launch on the current stream).  select_action does it
+        itself when an actor step was enqueued since the last re-pack; call this before capturing select_action in a
+        graph of your own, and inside that graph behind the learner's update if the graph holds both."""
+        self._actor_h.refresh()
+        self._stale = False
+        return self
+
+    def _live(self):
+        """select_action's packed actor.  No update reads it, so it is re-packed here, behind the actor steps enqueued since
+        the last call, rather than by a launch in every update."""
+        if self._stale:
+            self.refresh_actor()
+        return self._actor_h
+
+    def _load_modules(self, actor_ck, critic_ck, keys):
+        a, at, c, ct, ao, co = keys
+        self.actor.load_state_dict(actor_ck[a])
+        self.actor_target.load_state_dict(actor_ck[at])
+        self.critic.load_state_dict(critic_ck[c])
+        self.critic_target.load_state_dict(critic_ck[ct])
+        self._actor_adam.load_state_dict(actor_ck[ao])
+        self._critic_adam.load_state_dict(critic_ck[co])
+        self._set_updates(actor_ck.get("updates", 0))
+        self._graphs = None                 # a captured graph holds the addresses of the optimiser state it replaced
+        self.refresh()
+
+
+class FusedTD3(_ActorCriticLearner):
+    """td3.py's TD3 under the reference's attribute names; lr = 3e-4 on both optimisers (td3.py:81,85)."""
+    kind = _actor_lib.TD3
+    _noises = 1
+
+    def __init__(self, state_dim=10, action_dim=2, discount=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
+                 policy_freq=2, device="cuda", generator=None, log_capacity=1024, memory=None, hidden=256):
+        self.discount, self.tau, self.policy_noise, self.noise_clip = discount, tau, policy_noise, noise_clip
+        self.policy_freq = int(policy_freq)
+        if self.policy_freq < 1:
+            raise ValueError(f"uavx: policy_freq must be >= 1, got {policy_freq}")
+        self.max_action = 1
+        self._setup(device, generator, log_capacity, memory)
+        dev = self.device
+        self._dims = dict(state_dim=state_dim, action_dim=action_dim, hidden=hidden)
+        self.actor = policy.TD3Actor(state_dim, action_dim, hidden).to(dev)
+        self.actor_target = policy.TD3Actor(state_dim, action_dim, hidden).to(dev)
+        _copy_params(self.actor_target, self.actor)                                    # copy.deepcopy, td3.py:80
+        self.actor_optimizer = torch.optim.Adam(self.actor.parameters(), lr=3e-4)
+        self.critic = policy.TD3TwinQ(state_dim, action_dim, hidden).to(dev)
+        self.critic_target = policy.TD3TwinQ(state_dim, action_dim, hidden).to(dev)
+        _copy_params(self.critic_target, self.critic)
+        self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr=3e-4)
+        self._gamma = discount
+        self._build(policy_noise=policy_noise, noise_clip=noise_clip)
+
+    def _variants(self):
+        return (True,) if self.policy_freq == 1 else (True, False)
+
+    def _full(self, updates):
+        return updates % self.policy_freq == 0
+
+    def _update(self, s, a, r, s2, mask, noise, full):
+        y = self._target(s2, r, mask, generator=self.generator, noise=noise[0], out=self._target_out(s.shape[0]))
+        critic_loss = self._closs.backward(s, a, y)
+        self._critic_adam.step(update_target=False)
+        self._tail(critic_loss, self._actor_and_targets(s) if full else None)
+
+    def _throwaway(self):
+        return FusedTD3(device=self.device, log_capacity=1, **self._dims)
+
+    def select_action(self, obs, evaluate=True, noise_std=0.1, out=None):
+        """td3.py:95-97 over any batch of observations [..., 10] on the device; evaluate=False adds the trainer's clipped
+        Gaussian exploration noise (FusedActor.act).  The packed actor is re-packed by this call when an
+        actor step was enqueued since the last re-pack (a host flag): a capture of this call alone bakes in that re-pack or
+        its absence, so call refresh_actor() explicitly around captures of your own."""
+        return self._live().act(obs, evaluate=evaluate, generator=self.generator, noise_std=noise_std, out=out)
+
+    def save_checkpoint(self, ckpt_path, file_name=None):
+        """td3.py:159-170's file (policy.save_td3_checkpoint) with the targets as they are, plus the update count."""
+        path = os.path.join(ckpt_path, "weights.chpt" if file_name is None else file_name)
+        self._actor_adam.sync_state()
+        self._critic_adam.sync_state()
+        policy.save_td3_checkpoint(path, self.actor, self.critic, self.actor_optimizer, self.critic_optimizer)
+        _amend(path, {"actor_target_state_dict": _cpu(self.actor_target.state_dict()),
+                      "critic_target_state_dict": _cpu(self.critic_target.state_dict()),
+                      "updates": self.updates})
+        return path
+
+    def load_checkpoint(self, ckpt_path, file_name=None):
+        path = os.path.join(ckpt_path, "weights.chpt" if file_name is None else file_name)
+        ck = torch.load(path, map_location=self.device, weights_only=True)
+        self._load_modules(ck, ck, policy.TD3_CHECKPOINT_KEYS)
+        return self
+
+
+class FusedDDPG(_ActorCriticLearner):
+    """ddpg.py's DDPG under the reference's attribute names: AMSGrad on both optimisers, an L1 critic loss."""
+    kind = _actor_lib.DDPG
+    _noises = 0
+
+    def __init__(self, n_states=10, n_actions=2, noise_std_dev=0.2, actor_lr=1e-4, critic_lr=1e-3, tau=5e-3, gamma=0.99,
+                 device="cuda", generator=None, log_capacity=1024, memory=None, hidden1=400, hidden2=300):
+        self.n_states, self.n_actions = n_states, n_actions
+        self.noise_std_dev, self.tau, self.gamma = float(noise_std_dev), tau, gamma
+        self._setup(device, generator, log_capacity, memory)
+        dev = self.device
+        self._dims = dict(n_states=n_states, n_actions=n_actions, hidden1=hidden1, hidden2=hidden2)
+        self.actor = ddpg_init(policy.DDPGActor(n_states, n_actions, hidden1, hidden2), 5e-4).to(dev)     # model.py:8,19-22
+        self.actor_target = policy.DDPGActor(n_states, n_actions, hidden1, hidden2).to(dev)
+        self.actor_optimizer = torch.optim.Adam(self.actor.parameters(), lr=actor_lr, amsgrad=True)
+        self.critic = ddpg_init(policy.DDPGCritic(n_states, n_actions, hidden1, hidden2), 5e-5).to(dev)   # model.py:38,48-51
+        self.critic_target = policy.DDPGCritic(n_states, n_actions, hidden1, hidden2).to(dev)
+        self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr=critic_lr, amsgrad=True)
+        _copy_params(self.actor_target, self.actor)                                    # _hard_update, ddpg.py:27-28
+        _copy_params(self.critic_target, self.critic)
+        self._gamma = gamma
+        self._build()
+
+    def _update(self, s, a, r, s2, mask, noise, full):
+        y = self._target(s2, r, mask, out=self._target_out(s.shape[0]))
+        critic_loss = self._closs.backward(s, a, y)
+        self._critic_adam.step(update_target=False)
+        self._tail(critic_loss, self._actor_and_targets(s))
+
+    def _throwaway(self):
+        return FusedDDPG(device=self.device, log_capacity=1, **self._dims)
+
+    def select_action(self, obs, evaluate=False, noise=None, out=None):
+        """ddpg.py:39-47 over any batch of observations [..., 10] on the device.  evaluate=False adds `noise` (the caller's
+        Ornstein-Uhlenbeck state, a tensor broadcastable to the actions) and clips to [-1, 1].  The packed actor is re-packed by this call when an
+        actor step was enqueued since the last re-pack (a host flag): a capture of this call alone bakes in that re-pack or
+        its absence, so call refresh_actor() explicitly around captures of your own."""
+        return self._live().act(obs, evaluate=evaluate, noise=noise, out=out)
+
+    def save_checkpoint(self, output):
+        """ddpg.py:124-135's actor.chpt and critic.chpt in the directory `output` (policy.save_ddpg_checkpoint) with the
+        targets as they are, plus the update count."""
+        self._actor_adam.sync_state()
+        self._critic_adam.sync_state()
+        policy.save_ddpg_checkpoint(output, self.actor, self.critic, self.actor_optimizer, self.critic_optimizer)
+        _amend(os.path.join(output, "actor.chpt"), {"target_model_state_dict": _cpu(self.actor_target.state_dict()),
+                                                    "updates": self.updates})
+        _amend(os.path.join(output, "critic.chpt"),
+               {"target_model_state_dict": _cpu(self.critic_target.state_dict())})
+        return output
+
+    def load_checkpoint(self, output):
+        ack = torch.load(os.path.join(output, "actor.chpt"), map_location=self.device, weights_only=True)
+        cck = torch.load(os.path.join(output, "critic.chpt"), map_location=self.device, weights_only=True)
+        m, t, o = policy.DDPG_CHECKPOINT_KEYS
+        self._load_modules(ack, cck, (m, t, m, t, o, o))
+        return self

@@ -6,7 +6,7 @@ actor networks, so that checkpoint files written by the reference load unchanged
     DDPG  pytorch_ddpg_temp/  ActorNetwork (model.py:6-31)     actor.chpt    'model_state_dict'    (ddpg.py:124-135)
 Every actor emits a in [-1, 1]^2, which all three trainers convert the same way (test_sac_multi.py:77-80,
 test_td3_multi.py:77-79, test_ddpg_multi.py:78-80): feed it to step_ex(..., polar=True).
-The learners themselves are out of scope."""
+The learners built on these modules are in learners.py."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
