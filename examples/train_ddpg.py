@@ -1,0 +1,63 @@
+#!/usr/bin/env python3
+"""A closed DDPG training loop with nothing leaving the GPU between reports (test_ddpg_multi.py in batch form):
+UAVVectorEnv builds the worlds, DeviceReplay is the ring the step launch writes into, FusedDDPG replays its captured
+update, and an Exploration keeps one Ornstein-Uhlenbeck process per agent on the device (ou.py; ddpg.py:31,44 adds its one
+value to both action components), with uniform random actions while a row is in its warm-up.
+
+    python examples/train_ddpg.py [--envs 1024] [--agents 4] [--steps 2000] [--batch 256] [--warmup 64]
+                                  [--reset-ou-per-episode]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gym_uav_collision_avoidance_amd import UAVVectorEnv
+from gym_uav_collision_avoidance_amd.learners import FusedDDPG
+from gym_uav_collision_avoidance_amd.replay import DeviceReplay
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=1024)
+ap.add_argument("--agents", type=int, default=4)
+ap.add_argument("--steps", type=int, default=2000)
+ap.add_argument("--horizon", type=int, default=256)
+ap.add_argument("--batch", type=int, default=256)
+ap.add_argument("--warmup", type=int, default=64, help="steps every agent acts uniformly at random for (WARM_UP_STEPS)")
+ap.add_argument("--noise-std-dev", type=float, default=0.2, help="the OU process's std_deviation (ddpg.py:31)")
+ap.add_argument("--reset-ou-per-episode", action="store_true",
+                help="restart an env's OU processes when it begins an episode (the default never restarts them)")
+ap.add_argument("--updates-per-step", type=int, default=1)
+ap.add_argument("--report", type=int, default=500)
+ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--checkpoint", type=str, default=None, help="directory to write actor.chpt and critic.chpt into at the end")
+args = ap.parse_args()
+
+dev = torch.device("cuda", 0)
+venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=args.seed)
+mem = DeviceReplay(venv.env, horizon=args.horizon)
+mem.begin(venv.reset())
+agent = FusedDDPG(noise_std_dev=args.noise_std_dev, device=dev, memory=mem)
+explore = agent.exploration(mem, seed=args.seed, warmup_steps=args.warmup, reset_on_episode=args.reset_ou_per_episode)
+
+t0 = time.perf_counter()
+for t in range(args.steps):
+    agent.select_action(mem.state, explore=explore, out=mem.action_slot())     # forward + OU step, into the ring's slot
+    mem.step(polar=True, auto_reset="agent0_done", step_cap=1500, track_returns=True)
+    if t + 1 == args.warmup:
+        agent.capture(args.batch)                                              # sampling + the whole update, one graph
+    if t + 1 >= args.warmup:
+        agent.run(args.updates_per_step)
+    if (t + 1) % args.report == 0 and agent.updates:
+        q, _, pi = agent.losses(last=1)[0, :3]                                 # the one host read
+        print(f"step {t + 1}: {agent.updates} updates, critic {q:.4f} actor {pi:.4f}, OU |x| mean "
+              f"{float(explore.ou_state.abs().mean()):.4f}, {(t + 1) * args.envs / (time.perf_counter() - t0):,.0f} env steps/s")
+torch.cuda.synchronize()
+st = venv.episode_stats()
+print(f"{int(st['episodes'].sum())} episodes ended: {int(st['reach'].sum())} reached the goal, {int(st['coll'].sum())} collided")
+if args.checkpoint:
+    print("wrote", agent.save_checkpoint(args.checkpoint))
+agent.close()
+venv.close()

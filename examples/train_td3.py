@@ -1,0 +1,61 @@
+#!/usr/bin/env python3
+"""A closed TD3 training loop with nothing leaving the GPU between reports (test_td3_multi.py in batch form): UAVVectorEnv
+builds the worlds, DeviceReplay is the ring the step launch writes into, FusedTD3 replays its captured update, and an
+Exploration keeps the acting side on the device: uniform random actions while a row is in its warm-up, then the actor's
+action plus clipped Gaussian noise drawn from Philox streams keyed by the global agent.
+
+    python examples/train_td3.py [--envs 1024] [--agents 4] [--steps 2000] [--batch 256] [--warmup 64]
+"""
+import argparse
+import os
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from gym_uav_collision_avoidance_amd import UAVVectorEnv
+from gym_uav_collision_avoidance_amd.learners import FusedTD3
+from gym_uav_collision_avoidance_amd.replay import DeviceReplay
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--envs", type=int, default=1024)
+ap.add_argument("--agents", type=int, default=4)
+ap.add_argument("--steps", type=int, default=2000)
+ap.add_argument("--horizon", type=int, default=256)
+ap.add_argument("--batch", type=int, default=256)
+ap.add_argument("--warmup", type=int, default=64, help="steps every agent acts uniformly at random for (WARM_UP_STEPS)")
+ap.add_argument("--noise-std", type=float, default=0.1, help="standard deviation of the exploration noise")
+ap.add_argument("--updates-per-step", type=int, default=1)
+ap.add_argument("--report", type=int, default=500)
+ap.add_argument("--seed", type=int, default=0)
+ap.add_argument("--checkpoint", type=str, default=None, help="directory to write weights.chpt into at the end")
+args = ap.parse_args()
+
+dev = torch.device("cuda", 0)
+venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=args.seed)
+mem = DeviceReplay(venv.env, horizon=args.horizon)
+mem.begin(venv.reset())
+gen = torch.Generator(device=dev).manual_seed(args.seed)
+agent = FusedTD3(device=dev, generator=gen, memory=mem)
+explore = agent.exploration(mem, seed=args.seed, warmup_steps=args.warmup, noise_std=args.noise_std)
+
+t0 = time.perf_counter()
+for t in range(args.steps):
+    agent.select_action(mem.state, explore=explore, out=mem.action_slot())     # forward + exploration, into the ring's slot
+    mem.step(polar=True, auto_reset="agent0_done", step_cap=1500, track_returns=True)
+    if t + 1 == args.warmup:
+        agent.capture(args.batch)                                              # sampling + the whole update, one graph
+    if t + 1 >= args.warmup:
+        agent.run(args.updates_per_step)
+    if (t + 1) % args.report == 0 and agent.updates:
+        q1, q2, pi = agent.losses(last=1)[0, :3]                               # the one host read
+        print(f"step {t + 1}: {agent.updates} updates, critic {q1:.4f} {q2:.4f} actor {pi:.4f}, "
+              f"{(t + 1) * args.envs / (time.perf_counter() - t0):,.0f} env steps/s")
+torch.cuda.synchronize()
+st = venv.episode_stats()
+print(f"{int(st['episodes'].sum())} episodes ended: {int(st['reach'].sum())} reached the goal, {int(st['coll'].sum())} collided")
+if args.checkpoint:
+    print("wrote", agent.save_checkpoint(args.checkpoint))
+agent.close()
+venv.close()

@@ -1,7 +1,7 @@
 """ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h,
 include/uavx_optim.h, include/uavx_replay.h, include/uavx_action_grad.h, include/uavx_policy_grad.h,
-include/uavx_learner.h), the fused actor-inference, critic, TD-target, critic-gradient, optimiser-step, replay-sampling,
-critic action-gradient, actor forward / backward and learner-tail kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
+include/uavx_learner.h, include/uavx_explore.h), the fused actor-inference, critic, TD-target, critic-gradient, optimiser-step, replay-sampling,
+critic action-gradient, actor forward / backward, learner-tail and exploration kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
 that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
 missing library or device raises."""
 import ctypes
@@ -19,6 +19,7 @@ REPLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_replay.h")
 ACTION_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_action_grad.h")
 POLICY_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_policy_grad.h")
 LEARNER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_learner.h")
+EXPLORE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_explore.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
 ABI_VERSION = 1
 
@@ -62,6 +63,11 @@ POLICY_GRAD_MAX_ROWS = 262144   # UAVX_POLICY_GRAD_MAX_ROWS
 LEARNER_SYMBOLS = ("uavx_learner_version", "uavx_learner_tail")
 LEARNER_ABI_VERSION = 1
 LEARNER_LOG_COLUMNS = 8         # UAVX_LEARNER_LOG_COLUMNS
+# every symbol include/uavx_explore.h declares
+EXPLORE_SYMBOLS = ("uavx_explore_version", "uavx_explore_act")
+EXPLORE_ABI_VERSION = 1
+EXPLORE_MAX_ROWS = 16777216     # UAVX_EXPLORE_MAX_ROWS
+EXPLORE_STATE_BYTES = 16        # UAVX_EXPLORE_STATE_BYTES
 
 _lib_handle = None
 
@@ -72,15 +78,28 @@ class ReplayRing(ctypes.Structure):
                 + [(n, ctypes.c_int64) for n in ("slots", "envs", "agents", "learners")])
 
 
+class ExploreArgs(ctypes.Structure):
+    """uavx_explore_args of include/uavx_explore.h."""
+    _fields_ = [("kind", ctypes.c_int32), ("rows_per_env", ctypes.c_int32), ("rows", ctypes.c_int64),
+                ("row_offset", ctypes.c_int64), ("seed", ctypes.c_uint64), ("raw", ctypes.c_void_p),
+                ("raw_stride", ctypes.c_int64), ("out", ctypes.c_void_p), ("out_stride", ctypes.c_int64),
+                ("state", ctypes.c_void_p), ("normals", ctypes.c_void_p), ("normals_out", ctypes.c_void_p),
+                ("reset_flags", ctypes.c_void_p), ("reset_stride", ctypes.c_int64), ("reset_mask", ctypes.c_int32),
+                ("reserved", ctypes.c_int32), ("warmup_steps", ctypes.c_int64), ("random_prob_dev", ctypes.c_void_p),
+                ("random_prob", ctypes.c_float), ("noise_std", ctypes.c_float), ("ou_sigma", ctypes.c_double),
+                ("ou_theta", ctypes.c_double), ("ou_dt", ctypes.c_double), ("ou_mean", ctypes.c_double),
+                ("ou_x_initial", ctypes.c_double)]
+
+
 def _sources():
     import glob
     return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
             + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER,
-               POLICY_GRAD_HEADER, LEARNER_HEADER])
+               POLICY_GRAD_HEADER, LEARNER_HEADER, EXPLORE_HEADER])
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the eight headers of include/, plus
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the nine headers of include/, plus
     the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
     return _native.source_hash(CSRC, _sources())
 
@@ -162,6 +181,11 @@ def load():
         raise RuntimeError(f"{LIB_PATH} speaks learner ABI version {L.uavx_learner_version()}, this package binds "
                            f"{LEARNER_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
     L.uavx_learner_tail.argtypes = [i32, pvp, vp, f32, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, i64, vp, i32, vp]
+    L.uavx_explore_version.restype = i32
+    if L.uavx_explore_version() != EXPLORE_ABI_VERSION:
+        raise RuntimeError(f"{LIB_PATH} speaks exploration ABI version {L.uavx_explore_version()}, this package binds "
+                           f"{EXPLORE_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
+    L.uavx_explore_act.argtypes = [ctypes.POINTER(ExploreArgs), vp]
     _lib_handle = L
     return L
 

@@ -318,6 +318,28 @@ class _FusedLearner:
         self.updates = int(u)
         self._updates.fill_(self.updates)
 
+    def exploration(self, memory_or_rows, **kw):
+        """An Exploration (exploration.py) bound to the packed actor select_action acts with.
+        memory_or_rows: a DeviceReplay (every agent of every env acts: num_envs * num_agents rows; the ring is kept for
+        reset_on_episode) or the number of acting rows.  kw: Exploration's arguments; a learner's own noise scale is the
+        default (DDPG's ou_sigma = noise_std_dev, TD3's noise_std = 0.1)."""
+        from .exploration import Exploration
+        memory = None if isinstance(memory_or_rows, int) else memory_or_rows
+        rows = memory_or_rows if memory is None else memory.env.num_envs * memory.env.num_agents
+        for k, v in self._explore_defaults().items():
+            kw.setdefault(k, v)
+        ex = Exploration(self._actor_h, rows, **kw)
+        ex.memory = memory
+        return ex
+
+    def _explore_defaults(self):
+        return {}
+
+    def _explore(self, actor, explore, obs, out):
+        if explore.actor is not actor:
+            raise ValueError("uavx: this Exploration is bound to another actor; build it with this learner's exploration()")
+        return explore.act(obs, out=out)
+
     def refresh(self):
         """Re-packs every snapshot the kernels read: call it after writing into the modules by hand (load_state_dict);
         load_checkpoint does it itself."""
@@ -410,9 +432,12 @@ class FusedSAC(_FusedLearner):
         return FusedSAC(lr=self.lr, tau=self.tau, gamma=self.gamma, device=self.device, log_capacity=1,
                         automatic_entropy_tuning=self.automatic_entropy_tuning, **self._dims)
 
-    def select_action(self, obs, evaluate=False, out=None):
+    def select_action(self, obs, evaluate=False, out=None, explore=None):
         """sac.py:38-44 over any batch of observations [..., 10] on the device: tanh(mean + std·eps), or tanh(mean) when
-        evaluating; one launch on the packed live policy."""
+        evaluating; one launch on the packed live policy.  explore: an Exploration of this learner (exploration()): the
+        trainer's acting step with warm-up, random actions and Philox noise instead, two launches; `evaluate` is not read."""
+        if explore is not None:
+            return self._explore(self._actor_h, explore, obs, out)
         return self._actor_h.act(obs, evaluate=evaluate, generator=self.generator, out=out)
 
     def save_checkpoint(self, ckpt_path, file_name=None):
@@ -550,11 +575,18 @@ class FusedTD3(_ActorCriticLearner):
     def _throwaway(self):
         return FusedTD3(device=self.device, log_capacity=1, **self._dims)
 
-    def select_action(self, obs, evaluate=True, noise_std=0.1, out=None):
+    def _explore_defaults(self):
+        return {"noise_std": 0.1}
+
+    def select_action(self, obs, evaluate=True, noise_std=0.1, out=None, explore=None):
         """td3.py:95-97 over any batch of observations [..., 10] on the device; evaluate=False adds the trainer's clipped
         Gaussian exploration noise (FusedActor.act).  The packed actor is re-packed by this call when an
         actor step was enqueued since the last re-pack (a host flag): a capture of this call alone bakes in that re-pack or
-        its absence, so call refresh_actor() explicitly around captures of your own."""
+        its absence, so call refresh_actor() explicitly around captures of your own.  explore: an Exploration of this learner
+        (exploration()): the same re-pack, then the trainer's acting step with warm-up, random actions and Philox noise;
+        `evaluate` and `noise_std` are not read."""
+        if explore is not None:
+            return self._explore(self._live(), explore, obs, out)
         return self._live().act(obs, evaluate=evaluate, generator=self.generator, noise_std=noise_std, out=out)
 
     def save_checkpoint(self, ckpt_path, file_name=None):
@@ -607,11 +639,18 @@ class FusedDDPG(_ActorCriticLearner):
     def _throwaway(self):
         return FusedDDPG(device=self.device, log_capacity=1, **self._dims)
 
-    def select_action(self, obs, evaluate=False, noise=None, out=None):
+    def _explore_defaults(self):
+        return {"ou_sigma": self.noise_std_dev}
+
+    def select_action(self, obs, evaluate=False, noise=None, out=None, explore=None):
         """ddpg.py:39-47 over any batch of observations [..., 10] on the device.  evaluate=False adds `noise` (the caller's
         Ornstein-Uhlenbeck state, a tensor broadcastable to the actions) and clips to [-1, 1].  The packed actor is re-packed by this call when an
         actor step was enqueued since the last re-pack (a host flag): a capture of this call alone bakes in that re-pack or
-        its absence, so call refresh_actor() explicitly around captures of your own."""
+        its absence, so call refresh_actor() explicitly around captures of your own.  explore: an Exploration of this learner
+        (exploration()): the same re-pack, then the OU process kept on the device, with warm-up and random actions;
+        `evaluate` and `noise` are not read."""
+        if explore is not None:
+            return self._explore(self._live(), explore, obs, out)
         return self._live().act(obs, evaluate=evaluate, noise=noise, out=out)
 
     def save_checkpoint(self, output):
