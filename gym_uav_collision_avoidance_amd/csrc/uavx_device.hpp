@@ -54,6 +54,17 @@ __device__ __forceinline__ void store8_wt(rsrc_t r, uint32_t byte_off, float2 v)
     __builtin_amdgcn_raw_buffer_store_b64(d, r, (int)byte_off, 0, kAuxSc1);
 }
 
+// Lane L of a quad (four consecutive lanes) receives `v` of lane (L & ~3) + P<L & 3>: one DPP register move (v_mov_b32
+// quad_perm), no LDS.  The source lane has to be enabled in EXEC: call it where the whole quad is live.
+template <int P0, int P1, int P2, int P3>
+__device__ __forceinline__ uint32_t quad_perm(uint32_t v) {
+    return (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, P0 | (P1 << 2) | (P2 << 4) | (P3 << 6), 0xf, 0xf, true);
+}
+__device__ __forceinline__ float quad_perm_lane(float v, int k) {   // lane 4g of every quad: v of lane 4g + k (k = 1, 2, 3)
+    const uint32_t u = __float_as_uint(v);
+    return __uint_as_float(k == 1 ? quad_perm<1, 1, 1, 1>(u) : k == 2 ? quad_perm<2, 2, 2, 2>(u) : quad_perm<3, 3, 3, 3>(u));
+}
+
 // A kernel argument fetched WHERE IT IS USED.  The compiler treats the kernel-argument segment as invariant, dereferenceable
 // memory and hoists every scalar load from it to the top of the kernel, where the value then occupies scalar registers for the
 // whole life of the wavefront -- also the pointers that only a rare branch (an atomic on a goal arrival, a body's new waypoint)

@@ -31,7 +31,15 @@ __device__ __forceinline__ void assemble_obs(const H &h, const WorldLims &w, con
 // lane-major [64][10] tile is staged in LDS and written back with lane-contiguous vector stores.
 // Even N: a0 and cnt are even, so the block is 16-byte aligned and a whole number of float4
 // (uavx_create/step check the 16-byte alignment of the caller's obs pointer); otherwise float2.
-template <int NT, class LDS>
+// FLAT (step_kernel at N = 4; -DUAVX_OBSFLAT=0: off, A/B): the three store rounds without their
+// `f < nfloat` guards, so that the three LDS reads are issued together and the three stores follow instead of read -> wait ->
+// store -> restore EXEC three times in series.  Only the last workgroup can be partial; its rows beyond cnt lie at or above
+// nslot (a0 + cnt = E * N) and cnt * 40 B is a multiple of 16, so those stores are dropped whole by the buffer bounds check.
+// The tile is 2.5 rounds long: the upper half of the third round reads the tile's last row (in bounds) and stores out of range.
+#ifndef UAVX_OBSFLAT
+#define UAVX_OBSFLAT 1
+#endif
+template <int NT, class LDS, bool FLAT = false>
 __device__ __forceinline__ void store_obs_block(uint32_t nslot, int n_agents, const LaneMap &m, LDS &lds, const float o[10],
                                                 float *obs_out) {   // nslot = E * N, n_agents = N (read when NT == 0)
     constexpr int T = kWave * LDS::kW;
@@ -45,7 +53,22 @@ __device__ __forceinline__ void store_obs_block(uint32_t nslot, int n_agents, co
     const int nfloat = m.cnt * UAVX_OBS_DIM;
     const rsrc_t r = make_rsrc(obs_out, nslot * (UAVX_OBS_DIM * 4u));
     const uint32_t gbase = m.a0 * (UAVX_OBS_DIM * 4u);  // byte offset of the workgroup's block
-    if (NT ? (NT % 2 == 0) : ((n_agents & 1) == 0)) {   // uniform: even N => 16-byte aligned block of whole float4
+    if constexpr (UAVX_OBSFLAT && FLAT && NT != 0 && NT % 2 == 0 && LDS::kW == 1) {
+        constexpr int kTile = kWave * UAVX_OBS_DIM;
+        static_assert(kTile % 4 == 0 && 3 * T * 4 >= kTile, "three rounds of float4 cover the tile");
+        float4 v[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int f = (k * T + m.lane) * 4;
+            v[k] = *reinterpret_cast<const float4 *>(stage + ((k + 1) * T * 4 <= kTile ? f : min(f, kTile - 4)));
+        }
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+            const int f = (k * T + m.lane) * 4;
+            const uint32_t off = gbase + f * 4u;
+            store16_wt(r, ((k + 1) * T * 4 <= kTile || f < kTile) ? off : nslot * (UAVX_OBS_DIM * 4u), v[k]);
+        }
+    } else if (NT ? (NT % 2 == 0) : ((n_agents & 1) == 0)) {   // uniform: even N => 16-byte aligned block of whole float4
 #pragma unroll
         for (int k = 0; k < 3; k++) {
             const int f = (k * T + m.lane) * 4;
@@ -305,6 +328,11 @@ static_assert(sizeof(MultiParams) % 8 == 0, "fetch_step_args: `int evaluate` sta
 #endif
 template <int NT, bool EXT, int W, int T>
 constexpr bool step_fetches() { return UAVX_KFETCH && !EXT; }
+// The 4-UAV one-step kernel stores positions and rewards as quad-packed 16-byte write-through rows (-DUAVX_PACKWT=0: the plain
+// 8-byte / 4-byte stores, A/B).  Numbers: profiles/r13_packed_rows_ab.md.
+#ifndef UAVX_PACKWT
+#define UAVX_PACKWT 1
+#endif
 // T > 1: T independent one-wavefront tiles per workgroup (own LDS slice, wavefront-level ordering only) -- fewer workgroups for
 // the dispatcher to place.  Pays only where one-wavefront workgroups fill every slot exactly once and live short (65 536 x 8:
 // the 2.3 us over which 8 192 workgroups are placed is a large share of a 6 us wavefront); see tiles_for().
@@ -399,10 +427,32 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
             done_out[m.a] = (uint8_t)dn;
         } else {   // store_agent() through the buffer resources of the loads
             store16_wt(r_vel, m.a * 16u, make_double2(s.vx, s.vy));
+            const rsrc_t r_rew = make_rsrc(rew_out, nslot * 4u);
+#if UAVX_PACKWT
+            // Positions and rewards leave as 16-byte write-through rows too, assembled in registers: with N = 4 the lanes that
+            // hold 16 contiguous bytes are neighbours in a quad (positions: lanes 2k, 2k+1; rewards: lanes 4g .. 4g+3).
+            // A quad is ONE WHOLE ENV (whole envs are packed from thread 0 and slot = a0 + lane, lane_map_from), so inside
+            // `m.active` it is entirely live -- every DPP source lane is enabled -- and a row lies wholly inside nslot.
+            // Positions: agents 0 and 1 of the env store the rows of slots {0, 1} and {2, 3} (one compare on m.i; all four
+            // dwords arrive by DPP, so the row needs no copy of the lane's own x, y into a register quad)
+            const uint32_t ux = __float_as_uint(s.x), uy = __float_as_uint(s.y);
+            const float4 prow = make_float4(__uint_as_float(quad_perm<0, 2, 0, 2>(ux)), __uint_as_float(quad_perm<0, 2, 0, 2>(uy)),
+                                            __uint_as_float(quad_perm<1, 3, 1, 3>(ux)), __uint_as_float(quad_perm<1, 3, 1, 3>(uy)));
+            const float4 rrow = make_float4(rew, quad_perm_lane(rew, 1), quad_perm_lane(rew, 2), quad_perm_lane(rew, 3));
+            if (m.i < 2) store16_wt(r_pos, (m.a + (uint32_t)m.i) * 8u, prow);
+            // the reward array may be the caller's (out=, a replay-ring slot): rows only if it starts on a 16-byte boundary, else
+            // one dword per lane as before.  `mis` is uniform (a scalar test of the pointer: 0, or at least 4) and rides in the
+            // leaders' compare -- m.i == mis holds for agent 0 of an aligned array only -- so that the common path stays
+            // straight-line code under one EXEC mask, no scalar branch out and back
+            const uint32_t mis = ((uint32_t)reinterpret_cast<uintptr_t>(rew_out) & 15u) << 2;
+            if (__builtin_expect((uint32_t)m.i == mis, 1)) store16_wt(r_rew, m.a * 4u, rrow);
+            if (__builtin_expect(mis != 0u, 0)) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), r_rew, m.a * 4u, 0, 0);
+#else
             const u32x2 d = {__float_as_uint(s.x), __float_as_uint(s.y)};
             __builtin_amdgcn_raw_buffer_store_b64(d, r_pos, m.a * 8u, 0, 0);
+            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), r_rew, m.a * 4u, 0, 0);
+#endif
             if (s.flags != flags_in) __builtin_amdgcn_raw_buffer_store_b32(s.flags, r_goal, m.a * 16u + 12u, 0, 0);
-            __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), make_rsrc(rew_out, nslot * 4u), m.a * 4u, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)dn, make_rsrc(done_out, nslot), m.a, 0, 0);
         }
         // (FETCH: the counters' pointers are fetched inside their rare branches)
@@ -416,6 +466,8 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
             else atomicAdd(&ws[m.wave], 1u);                   // MUW:238 for every env of this wave (no-return)
         }
     }
-    if constexpr (FETCH) store_obs_block<NT>(nslot, (int)n_agents, m, lds, o, obs_out);   // (E, N: the preloaded leading scalars)
+    // (E, N: the preloaded leading scalars.  Flat store rounds at N = 4 only: at N = 2 and 8 the changed register allocation moved
+    //  the prev_ovr branch's scalar load next to its wait in the kernel's head, which tests/test_step_isa_host.py holds)
+    if constexpr (FETCH) store_obs_block<NT, LDS, NT == 4>(nslot, (int)n_agents, m, lds, o, obs_out);
     else store_obs_block<NT>(p, m, lds, o, obs_out);
 }
