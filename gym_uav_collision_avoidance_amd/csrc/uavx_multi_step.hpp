@@ -333,6 +333,26 @@ constexpr bool step_fetches() { return UAVX_KFETCH && !EXT; }
 #ifndef UAVX_PACKWT
 #define UAVX_PACKWT 1
 #endif
+// The tail of the same kernel (the two 4-UAV one-step instantiations only); numbers: profiles/r14_tail_ab.md.
+//   UAVX_TAILCOLD  flags word changed | arrival | hard collision | non-finite reward as ONE wave-uniform test and one scalar
+//                  branch; the four bodies sit in the block behind it (=0: four masked regions in line)
+//   UAVX_DONEROW   the env's four done bytes assembled in the quad and stored by its first lane as one write-through dword
+//                  (=0: one plain byte store per lane)
+// UAVX_CEIL_NOCOUNT / UAVX_CEIL_NODONE: ceiling builds for timing ONLY -- the step counter's increment / the done store
+// compiled out, wrong step counts / dones.  Never under a test.  (The counter's ceiling is 0.06 us; a load at the head and a
+// write-through store at the tail in place of its atomic measured 0.36 us SLOWER and is not kept.)
+#ifndef UAVX_TAILCOLD
+#define UAVX_TAILCOLD 1
+#endif
+#ifndef UAVX_DONEROW
+#define UAVX_DONEROW 1
+#endif
+#ifndef UAVX_CEIL_NOCOUNT
+#define UAVX_CEIL_NOCOUNT 0
+#endif
+#ifndef UAVX_CEIL_NODONE
+#define UAVX_CEIL_NODONE 0
+#endif
 // T > 1: T independent one-wavefront tiles per workgroup (own LDS slice, wavefront-level ordering only) -- fewer workgroups for
 // the dispatcher to place.  Pays only where one-wavefront workgroups fill every slot exactly once and live short (65 536 x 8:
 // the 2.3 us over which 8 192 workgroups are placed is a large share of a 6 us wavefront); see tiles_for().
@@ -350,6 +370,7 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
     // to spare) and the squared-distance neighbour scan (scan_neighbours)
     constexpr bool BUF = NT == 4 && !EXT && T == 1;
     constexpr bool FETCH = step_fetches<NT, EXT, W, T>();
+    constexpr bool TAILCOLD = BUF && UAVX_TAILCOLD;
     float2 *const pos_b = reinterpret_cast<float2 *>(slab);
     double2 *const vel_b = reinterpret_cast<double2 *>(slab + off_vel);
     Goal *const goal_b = reinterpret_cast<Goal *>(slab + off_goal);
@@ -444,23 +465,65 @@ __global__ __launch_bounds__(kWave * W * T, (EXT && W == 1) ? UAVX_STEPB : 1) vo
             // one dword per lane as before.  `mis` is uniform (a scalar test of the pointer: 0, or at least 4) and rides in the
             // leaders' compare -- m.i == mis holds for agent 0 of an aligned array only -- so that the common path stays
             // straight-line code under one EXEC mask, no scalar branch out and back
+#if UAVX_DONEROW && !UAVX_CEIL_NODONE
+            // The env's four done bytes (0 / 1 each) leave with the reward row, as one write-through dword from the same lane:
+            // two DPP steps ({d0 | d1 << 8, d2 | d3 << 8} in lanes 4g and 4g + 2, then the pair of pairs in lane 4g).  The
+            // leader's slot m.a is a multiple of 4 and its env lies wholly inside nslot.  A caller's done array that does not
+            // start on a 4-byte boundary gets its byte stores: its low address bits ride in `mis` too (one compare, one masked
+            // region and one fallback branch for both arrays; either array misaligned sends both down the narrow stores)
+            const rsrc_t r_done = make_rsrc(done_out, nslot);
+            const uint32_t dpair = dn | (quad_perm<1, 1, 3, 3>(dn) << 8);
+            const uint32_t drow = dpair | (quad_perm<2, 2, 2, 2>(dpair) << 16);
+            const uint32_t mis = (((uint32_t)reinterpret_cast<uintptr_t>(rew_out) & 15u) |
+                                  ((uint32_t)reinterpret_cast<uintptr_t>(done_out) & 3u)) << 2;
+            if (__builtin_expect((uint32_t)m.i == mis, 1)) {
+                store16_wt(r_rew, m.a * 4u, rrow);
+                __builtin_amdgcn_raw_buffer_store_b32(drow, r_done, m.a, 0, kAuxSc1);
+            }
+            if (__builtin_expect(mis != 0u, 0)) {
+                __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), r_rew, m.a * 4u, 0, 0);
+                __builtin_amdgcn_raw_buffer_store_b8((uint8_t)dn, r_done, m.a, 0, 0);
+            }
+#else
             const uint32_t mis = ((uint32_t)reinterpret_cast<uintptr_t>(rew_out) & 15u) << 2;
             if (__builtin_expect((uint32_t)m.i == mis, 1)) store16_wt(r_rew, m.a * 4u, rrow);
             if (__builtin_expect(mis != 0u, 0)) __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), r_rew, m.a * 4u, 0, 0);
+#endif
 #else
             const u32x2 d = {__float_as_uint(s.x), __float_as_uint(s.y)};
             __builtin_amdgcn_raw_buffer_store_b64(d, r_pos, m.a * 8u, 0, 0);
             __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(rew), r_rew, m.a * 4u, 0, 0);
 #endif
-            if (s.flags != flags_in) __builtin_amdgcn_raw_buffer_store_b32(s.flags, r_goal, m.a * 16u + 12u, 0, 0);
+            if constexpr (!TAILCOLD)
+                if (s.flags != flags_in) __builtin_amdgcn_raw_buffer_store_b32(s.flags, r_goal, m.a * 16u + 12u, 0, 0);
+#if !(UAVX_PACKWT && UAVX_DONEROW) && !UAVX_CEIL_NODONE
             __builtin_amdgcn_raw_buffer_store_b8((uint8_t)dn, make_rsrc(done_out, nslot), m.a, 0, 0);
+#endif
         }
-        // (FETCH: the counters' pointers are fetched inside their rare branches)
-        if (re) atomicAdd(&karg_if<FETCH>(p.reach, kStepLead + (uint32_t)offsetof(MultiParams, reach))[m.e], 1u);   // MUW:221
-        if (ce) atomicAdd(&karg_if<FETCH>(p.coll, kStepLead + (uint32_t)offsetof(MultiParams, coll))[m.e], 1u);     // MUW:209
-        if (!(fabsf(rew) < INFINITY))   // the tripwire of test_ddpg_multi.py:114-130, per env
-            atomicAdd(&karg_if<FETCH>(p.nonfin, kStepLead + (uint32_t)offsetof(MultiParams, nonfin))[m.e], 1u);
-        if (m.lane == 0) {
+        // The rare events.  TAILCOLD: ONE wave-uniform test on the common path and one scalar branch; the four bodies sit behind
+        // it.  An arrival sets DONE where it was clear and a counted collision sets COLLIDED where it was clear (step_agent), so
+        // `flags changed` already covers `re | ce`: the test is (flags changed) | (non-finite reward)
+        const bool nonfinite = !(fabsf(rew) < INFINITY);   // the tripwire of test_ddpg_multi.py:114-130, per env
+        if (!TAILCOLD || __builtin_expect(__any((s.flags != flags_in) | nonfinite), 0)) {
+            if constexpr (TAILCOLD)
+                if (s.flags != flags_in) __builtin_amdgcn_raw_buffer_store_b32(s.flags, r_goal, m.a * 16u + 12u, 0, 0);
+            // (FETCH: the counters' pointers are fetched inside their rare branches)
+            // TAILCOLD: the increment and the env index are made opaque here, so that the three branches share one register
+            // each instead of setting up their own (static vector instructions: tests/test_step4_isa_budget.py)
+            if constexpr (TAILCOLD) {
+                uint32_t one = 1u;
+                uint64_t ei = m.e;
+                asm volatile("" : "+v"(one), "+v"(ei));
+                if (re) atomicAdd(&karg_if<FETCH>(p.reach, kStepLead + (uint32_t)offsetof(MultiParams, reach))[ei], one);   // MUW:221
+                if (ce) atomicAdd(&karg_if<FETCH>(p.coll, kStepLead + (uint32_t)offsetof(MultiParams, coll))[ei], one);     // MUW:209
+                if (nonfinite) atomicAdd(&karg_if<FETCH>(p.nonfin, kStepLead + (uint32_t)offsetof(MultiParams, nonfin))[ei], one);
+            } else {
+                if (re) atomicAdd(&karg_if<FETCH>(p.reach, kStepLead + (uint32_t)offsetof(MultiParams, reach))[m.e], 1u);   // MUW:221
+                if (ce) atomicAdd(&karg_if<FETCH>(p.coll, kStepLead + (uint32_t)offsetof(MultiParams, coll))[m.e], 1u);     // MUW:209
+                if (nonfinite) atomicAdd(&karg_if<FETCH>(p.nonfin, kStepLead + (uint32_t)offsetof(MultiParams, nonfin))[m.e], 1u);
+            }
+        }
+        if (!(BUF && UAVX_CEIL_NOCOUNT) && m.lane == 0) {
             uint32_t *const ws = reinterpret_cast<uint32_t *>(slab + off_wsteps);
             if (EXT) ws[m.wave] = wave_count + 1u;             // single writer: this wave (MUW:238)
             else atomicAdd(&ws[m.wave], 1u);                   // MUW:238 for every env of this wave (no-return)
