@@ -1,8 +1,8 @@
 // Critic action-gradient (include/uavx_action_grad.h): q_t(s, a) and ∂q_t/∂a of the learners' actor update in ONE launch,
 // from the module's live parameters, with no weight gradients and no workspace.  DESIGN.md §17.
 //
-// All products run on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fmaf chain).  Lane l = 16·g + c of a wave holds
-// A[m = c][k = g] and B[k = g][n = c]; the accumulator element ii holds C[m = 4g + ii][n = c].
+// The lane layout of the MFMA products, layer 1, the z2 chain of a unit block and the eight-wave fold are shared with the
+// other gradient units: uavx_grad_impl.hpp.  The δ1 step is that header's too, but written out here (see the kernel).
 //
 //   action_grad   one workgroup of 8 waves per 16-row block and selected tower; rows are MFMA columns, units MFMA rows.
 //                 Layer 1 (f64, rounded once) into LDS.  Then ONE sweep over W2, wave w taking the 16-unit blocks
@@ -16,29 +16,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uavx_action_grad.h"
-#include "uavx_actor_impl.hpp"
+#include "uavx_grad_impl.hpp"
 
 namespace uavx_action_grad_k {
 
-using uavx_actor_k::act;
-using uavx_actor_k::f32x4;
+using namespace uavx_grad_k;
 
-constexpr int OBS = 10, IN = 12, WG = 512, WAVES = WG / 64, HALF = WAVES / 2;
-
-__device__ inline f32x4 mma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// torch's backward of the activation, given the pre-activation z (or the activation: the sign is the same) and the
-// incoming gradient d: relu: threshold_backward (z <= 0 gives 0; NaN passes), leaky_relu(0.01): z > 0 ? d : d·0.01
-template <bool LEAKY>
-__device__ inline float act_bwd(float z, float d) {
-    if constexpr (LEAKY) return z > 0.f ? d : d * 0.01f;
-    else return z <= 0.f ? 0.f : d;
-}
-template <bool LEAKY>
-__device__ inline double act_bwd(float z, double d) {
-    if constexpr (LEAKY) return z > 0.f ? d : d * 0.01;
-    else return z <= 0.f ? 0.0 : d;
-}
+constexpr int OBS = 10, IN = 12, WG = 512, WAVES = WG / 64;
 
 struct Args {
     const float *W1[2], *b1[2], *W2[2], *b2[2], *W3[2], *b3[2];
@@ -53,7 +37,7 @@ __global__ __launch_bounds__(WG) void action_grad(Args a) {
     constexpr int N1 = 16 * NB1, HP = N1 + 4;
     __shared__ float xs[16][IN];
     __shared__ __attribute__((aligned(16))) float h1s[16][HP];   // h1 of the block's rows (read as f32x4)
-    __shared__ f32x4 red[HALF][NB1][64];       // δ1ᵀ accumulators: waves 4..7, then (w + (w+4)) of waves 0..3
+    __shared__ f32x4 red[4][NB1][64];          // δ1ᵀ accumulators: waves 4..7, then (w + (w+4)) of waves 0..3
     __shared__ double qs[WAVES][16];
     __shared__ double js[WAVES][16][2];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15, wave = tid >> 6;
@@ -75,18 +59,8 @@ __global__ __launch_bounds__(WG) void action_grad(Args a) {
     }
     __syncthreads();
 
-    // ---- layer 1: h1 into LDS; 0 for padded units and padded rows
-    for (int e = tid; e < 16 * N1; e += WG) {
-        const int r = e / N1, i = e % N1;
-        float h = 0.f;
-        if (i < h1 && row0 + r < a.rows) {
-            double z = b1[i];                  // in f64, rounded once
-#pragma unroll
-            for (int k = 0; k < IN; ++k) z += (double)W1[i * IN + k] * (double)xs[r][k];
-            h = act<LEAKY>((float)z);
-        }
-        h1s[r][i] = h;
-    }
+    // ---- layer 1: h1 into LDS only
+    layer1<LEAKY, NB1, IN, WG>(W1, b1, xs, h1s, nullptr, h1, row0, a.rows, tid);
     __syncthreads();
 
     // ---- the one sweep over W2: per unit block z2, q and δ2 in registers, then δ1ᵀ += W2ᵀ·δ2ᵀ
@@ -98,27 +72,8 @@ __global__ __launch_bounds__(WG) void action_grad(Args a) {
         const int j = 16 * jb + c;             // this lane's A row
         const bool jin = j < h2;
         const float *w2 = W2 + (int64_t)(jin ? j : 0) * h1;
-        // each 16-wide k block is a 4-step fmaf chain of its own (rotating over four accumulators so that the MFMAs of
-        // neighbouring blocks overlap), added into f64: z2, and with it q, is rounded once, not once per k step
-        f32x4 acc4[4];
-        double zd[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kb = 0; kb < NB1; ++kb) {
-            const f32x4 hv = *(const f32x4 *)&h1s[c][16 * kb + 4 * g];
-            f32x4 &acc = acc4[kb & 3];
-            acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                // every load is unconditional, from a clamped address, and the value is selected afterwards: a load under
-                // a run-time condition is branched around and waited for one by one
-                const int k = 16 * kb + 4 * g + ii;
-                const bool kin = kb < NB1 - 1 || k < h1;                                  // h1 > 16·(NB1 − 1)
-                const float wv = w2[kin ? k : h1 - 1];
-                acc = mma(jin && kin ? wv : 0.f, hv[ii], acc);
-            }
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) zd[ii] += (double)acc[ii];
-        }
+        double zd[4];
+        z2_block<NB1, false>(w2, jin, h1, h1s, g, c, zd);
         f32x4 d2;
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii) {
@@ -129,6 +84,9 @@ __global__ __launch_bounds__(WG) void action_grad(Args a) {
             qp += (double)w3 * (double)act<LEAKY>(z);
             d2[ii] = rin && in ? act_bwd<LEAKY>(z, w3) : 0.f;   // dq/dq = 1: δ2 does not wait for q
         }
+        // uavx_grad_impl.hpp's delta1_block, written out: through the helper the compiler orders action_grad<true, 25>
+        // differently (same registers) and the launch measured 0.4 % slower at 65 536 rows
+        // (profiles/r17_grad_share_bench.jsonl); policy_bwd compiles the same either way and uses the helper
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii) {
             const int jj = 16 * jb + 4 * g + ii;
@@ -140,28 +98,17 @@ __global__ __launch_bounds__(WG) void action_grad(Args a) {
                 const float wv = w2r[iin ? i : h1 - 1];
                 dacc[ib] = mma(jj < h2 && iin ? wv : 0.f, d2[ii], dacc[ib]);
             }
-            // the 25-block tile: keep the scheduler from hoisting all 100 loads of the four steps at once, which spills
-            // (8 waves of 512 threads leave 256 registers a lane)
-            if constexpr (NB1 > 16) __builtin_amdgcn_sched_barrier(0);
+            if constexpr (NB1 > 16) __builtin_amdgcn_sched_barrier(0);   // see delta1_block
         }
     }
     qp += __shfl_xor(qp, 16);
     qp += __shfl_xor(qp, 32);
     if (g == 0) qs[wave][c] = qp;
 
-    // ---- δ1ᵀ over the waves, in a fixed order: waves 4..7 park theirs, waves 0..3 add their own to it in place
-    if (wave >= HALF) {
-#pragma unroll
-        for (int ib = 0; ib < NB1; ++ib) red[wave - HALF][ib][lane] = dacc[ib];
-    }
-    __syncthreads();
-    if (wave < HALF) {
-#pragma unroll
-        for (int ib = 0; ib < NB1; ++ib) red[wave][ib][lane] = dacc[ib] + red[wave][ib][lane];
-    }
-    __syncthreads();
+    // ---- δ1ᵀ over the waves: (w + (w+4)) for w = 0..3 in LDS, then
     // δ1 = (the four sums in wave order, f64) ⊙ act′(z1), over h1 in LDS (h1 > 0 exactly when z1 > 0; a NaN stays a NaN),
     // times the action columns of W1, summed over the units in f64
+    fold8<NB1>(red, dacc, wave, lane);
     double pj0 = 0.0, pj1 = 0.0;
     for (int ib = wave; ib < NB1; ib += WAVES) {
         const f32x4 r0 = red[0][ib][lane], r1 = red[1][ib][lane], r2 = red[2][ib][lane], r3 = red[3][ib][lane];

@@ -1,6 +1,7 @@
-// Definitions shared by the actor (uavx_actor.hip), critic (uavx_critic.hip) and critic-gradient (uavx_critic_grad.hip)
-// translation units of libuavx_actor.so: the packed-weight layout of one 3-layer MLP, the MFMA k order, the activations
-// and the actor and critic handles themselves.
+// Definitions shared by the translation units of libuavx_actor.so that work on the actor or the critic: uavx_actor.hip,
+// uavx_critic.hip, uavx_explore.hip (clampf) and, through uavx_grad_impl.hpp, the gradient units uavx_critic_grad.hip,
+// uavx_action_grad.hip, uavx_policy_grad.hip and uavx_grad_common.hip.  The packed-weight layout of one 3-layer MLP, the
+// MFMA k order, the activations and the actor and critic handles themselves.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -1,8 +1,8 @@
 // Critic-loss gradients (include/uavx_critic_grad.h): the forward with saved activations, the MSE / L1 loss and the
 // backward of the learners' critic update, in three launches.  DESIGN.md §14.
 //
-// All products run on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fmaf chain).  Lane l = 16·g + c of a wave holds
-// A[m = c][k = g] and B[k = g][n = c]; the accumulator element ii holds C[m = 4g + ii][n = c].
+// The lane layout of the MFMA products, layer 1, the W1 / b1 tail, the small helpers and the weights launch are shared with
+// the other gradient units: uavx_grad_impl.hpp.
 //
 //   1. grad_rows     one workgroup (4 waves) per 16-row block and tower; rows are MFMA columns, units MFMA rows.
 //                    Layer 1 (f64, rounded once) into LDS and to the workspace, for dW2; z2ᵀ = W2·h1ᵀ with wave w
@@ -12,38 +12,19 @@
 //                    δ1ᵀ += W2ᵀ·δ2ᵀ straight from the δ2 accumulator (its k order is the unit order of the block).  The
 //                    four waves' δ1 are summed through LDS in wave order.  The block's sums over its 16 rows of the
 //                    small gradients (W1, b1, b2, W3, b3) and of the loss go to a per-block partial row (f64).
-//   2. grad_weights  one wave per job: a 64 x 64 tile of dW2 = Σ_rows δ2ᵀ·h1 over one split-K slice of rows, or a
-//                    256-column slice of the per-block partial rows summed over the slice's blocks (f64).
+//   2. uavx_grad_k::grad_weights (uavx_grad_common.hip)  dW2 per split-K slice of rows and the partial rows per slice.
 //   3. grad_combine  one thread per output element: the split-K slices summed in slice order (f64), rounded once to f32
 //                    and written in torch layout; the loss divided by the row count.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uavx_critic_grad.h"
-#include "uavx_actor_impl.hpp"
+#include "uavx_grad_impl.hpp"
 
 namespace uavx_critic_grad_k {
 
-using uavx_actor_k::act;
-using uavx_actor_k::f32x4;
+using namespace uavx_grad_k;
 
 constexpr int OBS = 10, IN = 12, WG = 256, WAVES = WG / 64;
-
-__device__ inline f32x4 mma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// torch's backward of the activation, given the pre-activation z and the incoming gradient d:
-// relu: threshold_backward (z <= 0 gives 0; NaN passes), leaky_relu(0.01): z > 0 ? d : d·0.01
-template <bool LEAKY>
-__device__ inline float act_bwd(float z, float d) {
-    if constexpr (LEAKY) return z > 0.f ? d : d * 0.01f;
-    else return z <= 0.f ? 0.f : d;
-}
-
-// sum over the 16 lanes of a lane group (c = lane & 15) by butterfly: every lane ends with the same bits
-__device__ inline double sum16(double v) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 // offsets inside a per-block partial row (and inside the small-gradient slices): W1 [h1][12], b1, b2, W3, b3, loss
 struct Small {
@@ -105,23 +86,15 @@ __global__ __launch_bounds__(WG) void grad_rows(RowArgs a) {
     }
     __syncthreads();
 
-    // ---- layer 1: h1 into LDS and the workspace; 0 for padded units and padded rows
-    for (int e = tid; e < 16 * N1; e += WG) {
-        const int r = e / N1, i = e % N1;
-        float h = 0.f;
-        if (i < h1 && row0 + r < a.rows) {
-            double z = b1[i];                  // in f64, rounded once
-#pragma unroll
-            for (int k = 0; k < IN; ++k) z += (double)W1[i * IN + k] * (double)xs[r][k];
-            h = act<LEAKY>((float)z);
-        }
-        h1s[r][i] = h;
-        H1w[(int64_t)r * N1 + i] = h;
-    }
+    // ---- layer 1: h1 into LDS and the workspace, for dW2
+    layer1<LEAKY, NB1, IN, WG>(W1, b1, xs, h1s, H1w, h1, row0, a.rows, tid);
     __syncthreads();
 
     // ---- pass 1: z2 of the wave's unit blocks into the workspace, q folded per lane (in f64: dq is the only per-row value
-    // every gradient scales with)
+    // every gradient scales with).  This loop and pass 2's δ1 step are NOT uavx_grad_impl.hpp's z2_block / delta1_block /
+    // fold8: they load under a condition, not from a clamped address, run 4 waves and sum the waves' δ1 in f32, and
+    // grad_rows<true, 25> sits at 360 VGPRs.  Moving them to the clamped form is an optimisation with a measurement of its
+    // own, so the two forms stay apart, with no template switch between them.
     double qp = 0.0;
     for (int jb = wave; jb < a.nb2; jb += WAVES) {
         const int j = 16 * jb + c;             // this lane's A row
@@ -239,100 +212,8 @@ __global__ __launch_bounds__(WG) void grad_rows(RowArgs a) {
         }
     }
     __syncthreads();
-    // W1, b1 over the block's 16 rows: one (unit, input) pair per thread step, rows in order
-    for (int e = tid; e < h1 * 13; e += WG) {
-        const int i = e / 13, k = e % 13;
-        double s = 0.0;
-        if (k < IN) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += (double)h1s[r][i] * (double)xs[r][k];
-            P[sl.w1 + i * IN + k] = s;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += h1s[r][i];
-            P[sl.b1 + i] = s;
-        }
-    }
-}
-
-struct WeightArgs {
-    const float *h1ws, *d2ws;
-    const double *pws;
-    int64_t h1_tower, d2_tower, p_tower;
-    float *part2;                      // [S][towers][h2][h1]
-    double *partp;                     // [S][towers][lp]
-    int64_t b16, kc;
-    int h1, n1, h2, nb2, lp, towers, S, tj, ti, pchunks;
-};
-
-__global__ __launch_bounds__(WG) void grad_weights(WeightArgs a) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-    int64_t job = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
-    const int64_t tiles = (int64_t)a.towers * a.tj * a.ti;
-    if (job < tiles * a.S) {
-        // ---- a 64 x 64 tile of dW2 over rows [s·kc, (s+1)·kc): A = δ2ᵀ (units x rows), B = h1 (rows x inputs)
-        const int s = (int)(job / tiles);
-        const int64_t rem = job % tiles;
-        const int t = (int)(rem / (a.tj * a.ti)), tile = (int)(rem % (a.tj * a.ti));
-        const int j0 = 64 * (tile / a.ti), i0 = 64 * (tile % a.ti), ld2 = 16 * a.nb2;
-        const float *D = a.d2ws + t * a.d2_tower, *H = a.h1ws + t * a.h1_tower;
-        const int64_t r_lo = s * a.kc, r_hi = r_lo + a.kc < a.b16 ? r_lo + a.kc : a.b16;
-        int jm[4], in_[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            jm[m] = j0 + 16 * m + c;
-            in_[m] = i0 + 16 * m + c;
-        }
-        f32x4 acc[4][4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int64_t r = r_lo; r < r_hi; r += 4) {
-            const float *dr = D + (r + g) * ld2, *hr = H + (r + g) * a.n1;
-            float av[4], bv[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                av[m] = jm[m] < a.h2 ? dr[jm[m]] : 0.f;
-                bv[m] = in_[m] < a.h1 ? hr[in_[m]] : 0.f;
-            }
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = mma(av[m], bv[n], acc[m][n]);
-        }
-        float *out = a.part2 + ((int64_t)s * a.towers + t) * a.h2 * a.h1;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                const int j = j0 + 16 * m + 4 * g + ii;
-                if (j >= a.h2) continue;
-#pragma unroll
-                for (int n = 0; n < 4; ++n)
-                    if (in_[n] < a.h1) out[(int64_t)j * a.h1 + in_[n]] = acc[m][n][ii];
-            }
-        return;
-    }
-    job -= tiles * a.S;
-    const int64_t pjobs = (int64_t)a.towers * a.pchunks;
-    if (job >= pjobs * a.S) return;
-    // ---- 256 columns of the per-block partial rows summed over the blocks of slice s, in block order, in f64
-    const int s = (int)(job / pjobs);
-    const int t = (int)(job % pjobs / a.pchunks), chunk = (int)(job % a.pchunks);
-    const int e0 = 256 * chunk + 4 * lane;
-    if (e0 >= a.lp) return;
-    const int64_t w_lo = s * (a.kc / 16), w_end = (s + 1) * (a.kc / 16), nblk = a.b16 / 16;
-    const int64_t w_hi = w_end < nblk ? w_end : nblk;
-    const double *P = a.pws + t * a.p_tower + e0;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t w = w_lo; w < w_hi; ++w) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] += P[w * a.lp + q];
-    }
-    double *out = a.partp + ((int64_t)s * a.towers + t) * a.lp + e0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[q] = acc[q];
+    // W1, b1 over the block's 16 rows
+    w1b1_tail<WG>(h1s, xs, P, sl.w1, sl.b1, h1, tid);
 }
 
 struct CombineArgs {
@@ -378,8 +259,6 @@ struct Plan {
     int64_t b16, kc, h1_tower, d2_tower, p_tower, off_d2, off_p, off_part2, off_partp, bytes;
 };
 
-int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 Plan plan(const uavx_critic *h, int64_t rows) {
     Plan p;
     const int T = h->towers;
@@ -390,13 +269,7 @@ Plan plan(const uavx_critic *h, int64_t rows) {
     p.ti = (h->h1 + 63) / 64;
     p.pchunks = (p.lp + 255) / 256;
     p.b16 = (rows + 15) / 16 * 16;
-    // split-K: about 8192 tile jobs, slices of at least 64 rows (a multiple of 16: whole row blocks)
-    const int64_t tiles = (int64_t)T * p.tj * p.ti, by_rows = (p.b16 + 63) / 64;
-    int64_t S = 8192 / tiles;
-    if (S < 1) S = 1;
-    if (S > by_rows) S = by_rows;
-    p.kc = ((p.b16 + S - 1) / S + 15) / 16 * 16;
-    p.S = (int)((p.b16 + p.kc - 1) / p.kc);
+    split_k((int64_t)T * p.tj * p.ti, p.b16, &p.kc, &p.S);
     p.h1_tower = p.b16 * p.n1;
     p.d2_tower = p.b16 * 16 * p.nb2;
     p.p_tower = p.b16 / 16 * p.lp;
@@ -503,9 +376,7 @@ int uavx_critic_grad(const uavx_critic *h, int loss, const float *const *params,
     wa.tj = p.tj;
     wa.ti = p.ti;
     wa.pchunks = p.pchunks;
-    const int64_t jobs = ((int64_t)T * p.tj * p.ti + (int64_t)T * p.pchunks) * p.S;
-    hipLaunchKernelGGL(grad_weights, dim3((unsigned)((jobs + WAVES - 1) / WAVES)), dim3(WG), 0, st, wa);
-    if (hipGetLastError() != hipSuccess) return UAVX_CRITIC_ERR_HIP;
+    if (!launch_grad_weights(wa, st)) return UAVX_CRITIC_ERR_HIP;
 
     CombineArgs ca{};
     ca.part2 = wa.part2;

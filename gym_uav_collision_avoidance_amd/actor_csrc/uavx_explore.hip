@@ -12,8 +12,11 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/uavx_explore.h"
+#include "uavx_actor_impl.hpp"
 
 namespace uavx_explore_k {
+
+using uavx_actor_k::clampf;
 
 constexpr int BLOCK = 256;
 
@@ -55,10 +58,6 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c0, uint32_t c1, uint32_t
         k1 += 0xBB67AE85u;
     }
     w[0] = c0; w[1] = c1; w[2] = c2; w[3] = c3;
-}
-
-__device__ __forceinline__ float clampf(float x, float lo, float hi) {   // uavx_actor_impl.hpp's: NaN stays NaN
-    return x < lo ? lo : (x > hi ? hi : x);
 }
 
 template <int KIND>

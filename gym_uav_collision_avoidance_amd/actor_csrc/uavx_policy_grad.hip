@@ -2,8 +2,8 @@
 // from the actor's live parameters, and, once the critic's q and ∂q/∂a are known, every actor parameter's gradient, the
 // loss and SAC's mean logπ.  Four launches of this unit around the one of uavx_action_grad.  DESIGN.md §18.
 //
-// All products run on v_mfma_f32_16x16x4_f32 (exact f32, a k-ordered fmaf chain).  Lane l = 16·g + c of a wave holds
-// A[m = c][k = g] and B[k = g][n = c]; the accumulator element ii holds C[m = 4g + ii][n = c].
+// The lane layout of the MFMA products, layer 1, the z2 chain and the δ1 step of a unit block, the eight-wave fold, the
+// W1 / b1 tail, the small helpers and the weights launch are shared with the other gradient units: uavx_grad_impl.hpp.
 //
 //   1. policy_fwd      one workgroup of 8 waves per 16-row block; rows are MFMA columns, units MFMA rows.  Layer 1 (f64,
 //                      rounded once) into LDS and to the workspace, for dW2; z2ᵀ = W2·h1ᵀ with wave w taking the 16-unit
@@ -17,40 +17,22 @@
 //                      summed through LDS in a fixed order, (w + (w+4)) for w = 0..3 in f32 and those four in wave order
 //                      in f64.  The block's sums over its 16 rows of the small gradients (W1, b1, b2, W3, b3), of the
 //                      loss and of logπ go to a per-block partial row (f64).
-//   4. policy_weights  one wave per job: a 64 x 64 tile of dW2 = Σ_rows δ2ᵀ·h1 over one split-K slice of rows, or a
-//                      256-column slice of the per-block partial rows summed over the slice's blocks (f64).
+//   4. uavx_grad_k::grad_weights (uavx_grad_common.hip), one tower  dW2 per split-K slice of rows and the partial rows
+//                      per slice.
 //   5. policy_combine  one thread per output element: the split-K slices summed in slice order (f64), rounded once to f32
 //                      and written in torch layout; the loss and logπ sums divided by the row count.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uavx_policy_grad.h"
-#include "uavx_actor_impl.hpp"
+#include "uavx_grad_impl.hpp"
 
 namespace uavx_policy_grad_k {
 
-using uavx_actor_k::act;
-using uavx_actor_k::f32x4;
+using namespace uavx_grad_k;
 
-constexpr int OBS = 10, WG = 512, WAVES = WG / 64, HALF = WAVES / 2, REC = 8, CWG = 256, CWAVES = CWG / 64;
+constexpr int OBS = 10, WG = 512, WAVES = WG / 64, REC = 8, CWG = 256;   // CWG: the combine kernel's workgroup
 // a row's head record in the workspace
 constexpr int R_T = 0, R_U = 2, R_SE = 4, R_MASK = 6, R_LOGPI = 7;
-
-__device__ inline f32x4 mma(float a, float b, f32x4 c) { return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0); }
-
-// torch's backward of the activation, given the pre-activation z (or the activation: the sign is the same) and the
-// incoming gradient d: relu: threshold_backward (z <= 0 gives 0; NaN passes), leaky_relu(0.01): z > 0 ? d : d·0.01
-template <bool LEAKY>
-__device__ inline double act_bwd(float z, double d) {
-    if constexpr (LEAKY) return z > 0.f ? d : d * 0.01;
-    else return z <= 0.f ? 0.0 : d;
-}
-
-// sum over the 16 lanes of a lane group (c = lane & 15) by butterfly: every lane ends with the same bits
-__device__ inline double sum16(double v) {
-#pragma unroll
-    for (int m = 1; m < 16; m <<= 1) v += __shfl_xor(v, m);
-    return v;
-}
 
 // offsets inside a per-block partial row (and inside the small-gradient slices): W1 [h1][10], b1, b2, W3 [O][h2], b3 [O],
 // loss, Σ logπ
@@ -104,19 +86,8 @@ __global__ __launch_bounds__(WG) void policy_fwd(FwdArgs a) {
     }
     __syncthreads();
 
-    // ---- layer 1: h1 into LDS and the workspace; 0 for padded units and padded rows
-    for (int e = tid; e < 16 * N1; e += WG) {
-        const int r = e / N1, i = e % N1;
-        float h = 0.f;
-        if (i < h1 && row0 + r < a.rows) {
-            double z = b1[i];                  // in f64, rounded once
-#pragma unroll
-            for (int k = 0; k < OBS; ++k) z += (double)W1[i * OBS + k] * (double)xs[r][k];
-            h = act<LEAKY>((float)z);
-        }
-        h1s[r][i] = h;
-        H1w[(int64_t)r * N1 + i] = h;
-    }
+    // ---- layer 1: h1 into LDS and the workspace, for dW2
+    layer1<LEAKY, NB1, OBS, WG>(W1, b1, xs, h1s, H1w, h1, row0, a.rows, tid);
     __syncthreads();
 
     // ---- the sweep over W2: z2 of the wave's unit blocks into the workspace, the head rows folded per lane in f64
@@ -125,30 +96,8 @@ __global__ __launch_bounds__(WG) void policy_fwd(FwdArgs a) {
         const int j = 16 * jb + c;             // this lane's A row
         const bool jin = j < h2;
         const float *w2 = W2 + (int64_t)(jin ? j : 0) * h1;
-        // each 16-wide k block is a 4-step fmaf chain of its own (rotating over four accumulators so that the MFMAs of
-        // neighbouring blocks overlap), added into f64: z2 is rounded once, not once per k step
-        f32x4 acc4[4];
-        double zd[4] = {0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-        for (int kb = 0; kb < NB1; ++kb) {
-            const f32x4 hv = *(const f32x4 *)&h1s[c][16 * kb + 4 * g];
-            f32x4 &acc = acc4[kb & 3];
-            acc = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                // every load is unconditional, from a clamped address, and the value is selected afterwards
-                const int k = 16 * kb + 4 * g + ii;
-                const bool kin = kb < NB1 - 1 || k < h1;                                  // h1 > 16·(NB1 − 1)
-                const float wv = w2[kin ? k : h1 - 1];
-                acc = mma(jin && kin ? wv : 0.f, hv[ii], acc);
-            }
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) zd[ii] += (double)acc[ii];
-            // the 25-block tile: keep the scheduler from hoisting all 100 loads of the row at once, which spills
-            if constexpr (NB1 > 16) {
-                if ((kb & 7) == 7) __builtin_amdgcn_sched_barrier(0);
-            }
-        }
+        double zd[4];
+        z2_block<NB1, (NB1 > 16)>(w2, jin, h1, h1s, g, c, zd);   // the 25-block tile spills without the barrier
         f32x4 z;
 #pragma unroll
         for (int ii = 0; ii < 4; ++ii) {
@@ -246,7 +195,7 @@ __global__ __launch_bounds__(WG) void policy_bwd(BwdArgs a) {
     constexpr int N1 = 16 * NB1, HP = N1 + 4;
     __shared__ float xs[16][OBS];
     __shared__ float h1s[16][HP];              // h1 of the block's rows; δ1 at the end
-    __shared__ f32x4 red[HALF][NB1][64];       // δ1ᵀ accumulators: waves 4..7, then (w + (w+4)) of waves 0..3
+    __shared__ f32x4 red[4][NB1][64];          // δ1ᵀ accumulators: waves 4..7, then (w + (w+4)) of waves 0..3
     __shared__ double d3s[16][4];
     __shared__ double ls[16], lps[16];
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, c = lane & 15, wave = tid >> 6;
@@ -346,35 +295,12 @@ __global__ __launch_bounds__(WG) void policy_bwd(BwdArgs a) {
             }
         }
         *zp = d2;
-#pragma unroll
-        for (int ii = 0; ii < 4; ++ii) {
-            const int jj = 16 * jb + 4 * g + ii;
-            const float *w2r = W2 + (int64_t)(jj < h2 ? jj : 0) * h1;
-#pragma unroll
-            for (int ib = 0; ib < NB1; ++ib) {
-                const int i = 16 * ib + c;
-                const bool iin = ib < NB1 - 1 || i < h1;
-                const float wv = w2r[iin ? i : h1 - 1];
-                dacc[ib] = mma(jj < h2 && iin ? wv : 0.f, d2[ii], dacc[ib]);
-            }
-            // the 25-block tile: keep the scheduler from hoisting all 100 loads of the four steps at once, which spills
-            // (8 waves of 512 threads leave 256 registers a lane)
-            if constexpr (NB1 > 16) __builtin_amdgcn_sched_barrier(0);
-        }
+        delta1_block<NB1>(W2, jb, h1, h2, d2, g, c, dacc);
     }
 
-    // ---- δ1ᵀ over the waves, in a fixed order: waves 4..7 park theirs, waves 0..3 add their own to it in place
-    if (wave >= HALF) {
-#pragma unroll
-        for (int ib = 0; ib < NB1; ++ib) red[wave - HALF][ib][lane] = dacc[ib];
-    }
-    __syncthreads();
-    if (wave < HALF) {
-#pragma unroll
-        for (int ib = 0; ib < NB1; ++ib) red[wave][ib][lane] = dacc[ib] + red[wave][ib][lane];
-    }
-    __syncthreads();
+    // ---- δ1ᵀ over the waves: (w + (w+4)) for w = 0..3 in LDS, then
     // δ1 = (the four sums in wave order, f64) ⊙ act′(z1), over h1 in LDS (h1 > 0 exactly when z1 > 0; a NaN stays a NaN)
+    fold8<NB1>(red, dacc, wave, lane);
     for (int ib = wave; ib < NB1; ib += WAVES) {
         const f32x4 r0 = red[0][ib][lane], r1 = red[1][ib][lane], r2 = red[2][ib][lane], r3 = red[3][ib][lane];
 #pragma unroll
@@ -386,94 +312,8 @@ __global__ __launch_bounds__(WG) void policy_bwd(BwdArgs a) {
         }
     }
     __syncthreads();
-    // W1, b1 over the block's 16 rows: one (unit, input) pair per thread step, rows in order
-    for (int e = tid; e < h1 * (OBS + 1); e += WG) {
-        const int i = e / (OBS + 1), k = e % (OBS + 1);
-        double s = 0.0;
-        if (k < OBS) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += (double)h1s[r][i] * (double)xs[r][k];
-            P[sl.w1 + i * OBS + k] = s;
-        } else {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) s += h1s[r][i];
-            P[sl.b1 + i] = s;
-        }
-    }
-}
-
-struct WeightArgs {
-    const float *h1ws, *d2ws;
-    const double *pws;
-    float *part2;                      // [S][h2][h1]
-    double *partp;                     // [S][lp]
-    int64_t b16, kc;
-    int h1, n1, h2, nb2, lp, S, tj, ti, pchunks;
-};
-
-__global__ __launch_bounds__(CWG) void policy_weights(WeightArgs a) {
-    const int lane = threadIdx.x & 63, g = lane >> 4, c = lane & 15;
-    int64_t job = (int64_t)blockIdx.x * CWAVES + (threadIdx.x >> 6);
-    const int64_t tiles = (int64_t)a.tj * a.ti;
-    if (job < tiles * a.S) {
-        // ---- a 64 x 64 tile of dW2 over rows [s·kc, (s+1)·kc): A = δ2ᵀ (units x rows), B = h1 (rows x inputs)
-        const int s = (int)(job / tiles), tile = (int)(job % tiles);
-        const int j0 = 64 * (tile / a.ti), i0 = 64 * (tile % a.ti), ld2 = 16 * a.nb2;
-        const int64_t r_lo = s * a.kc, r_hi = r_lo + a.kc < a.b16 ? r_lo + a.kc : a.b16;
-        int jm[4], in_[4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m) {
-            jm[m] = j0 + 16 * m + c;
-            in_[m] = i0 + 16 * m + c;
-        }
-        f32x4 acc[4][4];
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int n = 0; n < 4; ++n) acc[m][n] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int64_t r = r_lo; r < r_hi; r += 4) {
-            const float *dr = a.d2ws + (r + g) * ld2, *hr = a.h1ws + (r + g) * a.n1;
-            float av[4], bv[4];
-#pragma unroll
-            for (int m = 0; m < 4; ++m) {
-                av[m] = jm[m] < a.h2 ? dr[jm[m]] : 0.f;
-                bv[m] = in_[m] < a.h1 ? hr[in_[m]] : 0.f;
-            }
-#pragma unroll
-            for (int m = 0; m < 4; ++m)
-#pragma unroll
-                for (int n = 0; n < 4; ++n) acc[m][n] = mma(av[m], bv[n], acc[m][n]);
-        }
-        float *out = a.part2 + (int64_t)s * a.h2 * a.h1;
-#pragma unroll
-        for (int m = 0; m < 4; ++m)
-#pragma unroll
-            for (int ii = 0; ii < 4; ++ii) {
-                const int j = j0 + 16 * m + 4 * g + ii;
-                if (j >= a.h2) continue;
-#pragma unroll
-                for (int n = 0; n < 4; ++n)
-                    if (in_[n] < a.h1) out[(int64_t)j * a.h1 + in_[n]] = acc[m][n][ii];
-            }
-        return;
-    }
-    job -= tiles * a.S;
-    if (job >= (int64_t)a.pchunks * a.S) return;
-    // ---- 256 columns of the per-block partial rows summed over the blocks of slice s, in block order, in f64
-    const int s = (int)(job / a.pchunks), chunk = (int)(job % a.pchunks);
-    const int e0 = 256 * chunk + 4 * lane;
-    if (e0 >= a.lp) return;
-    const int64_t w_lo = s * (a.kc / 16), w_end = (s + 1) * (a.kc / 16), nblk = a.b16 / 16;
-    const int64_t w_hi = w_end < nblk ? w_end : nblk;
-    const double *P = a.pws + e0;
-    double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    for (int64_t w = w_lo; w < w_hi; ++w) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] += P[w * a.lp + q];
-    }
-    double *out = a.partp + (int64_t)s * a.lp + e0;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) out[q] = acc[q];
+    // W1, b1 over the block's 16 rows
+    w1b1_tail<WG>(h1s, xs, P, sl.w1, sl.b1, h1, tid);
 }
 
 struct CombineArgs {
@@ -524,8 +364,6 @@ struct Plan {
     int64_t b16, kc, off_z2, off_rec, off_p, off_part2, off_partp, bytes;
 };
 
-int64_t align256(int64_t x) { return (x + 255) & ~(int64_t)255; }
-
 Plan plan(int kind, int h1, int h2, int64_t rows) {
     Plan p;
     p.n1 = (h1 + 15) / 16 * 16;
@@ -536,13 +374,7 @@ Plan plan(int kind, int h1, int h2, int64_t rows) {
     p.ti = (h1 + 63) / 64;
     p.pchunks = (p.lp + 255) / 256;
     p.b16 = (rows + 15) / 16 * 16;
-    // split-K: about 8192 tile jobs, slices of at least 64 rows (a multiple of 16: whole row blocks)
-    const int64_t tiles = (int64_t)p.tj * p.ti, by_rows = (p.b16 + 63) / 64;
-    int64_t S = 8192 / tiles;
-    if (S < 1) S = 1;
-    if (S > by_rows) S = by_rows;
-    p.kc = ((p.b16 + S - 1) / S + 15) / 16 * 16;
-    p.S = (int)((p.b16 + p.kc - 1) / p.kc);
+    split_k((int64_t)p.tj * p.ti, p.b16, &p.kc, &p.S);
     p.off_z2 = align256(p.b16 * p.n1 * 4);
     p.off_rec = p.off_z2 + align256(p.b16 * 16 * p.nb2 * 4);
     p.off_p = p.off_rec + align256(p.b16 * REC * 4);
@@ -667,7 +499,7 @@ int uavx_policy_grad_backward(int kind, int hidden1, int hidden2, const float *c
     hipLaunchKernelGGL(fb, dim3((unsigned)(p.b16 / 16)), dim3(WG), 0, st, ba);
     if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
 
-    WeightArgs wa{};
+    WeightArgs wa{};                           // one tower: the tower strides stay 0
     wa.h1ws = ba.h1ws;
     wa.d2ws = ba.d2ws;
     wa.pws = ba.pws;
@@ -680,13 +512,12 @@ int uavx_policy_grad_backward(int kind, int hidden1, int hidden2, const float *c
     wa.h2 = hidden2;
     wa.nb2 = p.nb2;
     wa.lp = p.lp;
+    wa.towers = 1;
     wa.S = p.S;
     wa.tj = p.tj;
     wa.ti = p.ti;
     wa.pchunks = p.pchunks;
-    const int64_t jobs = ((int64_t)p.tj * p.ti + p.pchunks) * p.S;
-    hipLaunchKernelGGL(policy_weights, dim3((unsigned)((jobs + CWAVES - 1) / CWAVES)), dim3(CWG), 0, st, wa);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
+    if (!launch_grad_weights(wa, st)) return UAVX_ACTOR_ERR_HIP;
 
     CombineArgs ca{};
     ca.part2 = wa.part2;

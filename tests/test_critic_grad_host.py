@@ -83,8 +83,16 @@ def test_grad_kernels_no_spills_no_scratch():
     grad = [r for r in rows if r["name"].startswith("uavx_critic_grad_k::")]
     names = sorted(r["name"] for r in grad)
     assert names == ["uavx_critic_grad_k::grad_combine", "uavx_critic_grad_k::grad_rows<false, 16>",
-                     "uavx_critic_grad_k::grad_rows<true, 25>", "uavx_critic_grad_k::grad_weights"], names
-    for r in grad:
+                     "uavx_critic_grad_k::grad_rows<true, 25>"], names
+    # the dW2 weights kernel this unit shares with the actor backward (actor_csrc/uavx_grad_common.hip)
+    shared = [r for r in rows if r["name"].startswith("uavx_grad_k::")]
+    assert [r["name"] for r in shared] == ["uavx_grad_k::grad_weights"], shared
+    for r in shared:
+        assert r["group_segment_fixed_size"] == 0, r
+        # what grad_weights and policy_weights each used before they became one kernel.  vgpr_count is the unified
+        # register file's total (.amdhsa_next_free_vgpr): the 64 accumulator registers of the 4 x 4 tile are part of it
+        assert r["vgpr_count"] <= 92 and r["agpr_count"] <= 64, r
+    for r in grad + shared:
         assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0, r
         assert r["private_segment_fixed_size"] == 0, r
         assert r["max_flat_workgroup_size"] == 256, r
