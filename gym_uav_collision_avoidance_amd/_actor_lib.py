@@ -1,71 +1,35 @@
-"""ctypes binding of libuavx_actor.so (include/uavx_actor.h, include/uavx_critic.h, include/uavx_critic_grad.h,
-include/uavx_optim.h, include/uavx_replay.h, include/uavx_action_grad.h, include/uavx_policy_grad.h,
-include/uavx_learner.h, include/uavx_explore.h), the fused actor-inference, critic, TD-target, critic-gradient, optimiser-step, replay-sampling,
-critic action-gradient, actor forward / backward, learner-tail and exploration kernels.  Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so
-that the environment library and the source hash its profiles carry do not change with it.  There is NO fallback: a
-missing library or device raises."""
+"""ctypes binding of libuavx_actor.so: the fused actor, critic, TD-target, gradient, optimiser, replay, learner-tail and
+exploration kernels.  UNITS describes its nine units once -- header, bound ABI version, every exported function with its
+restype and argtypes -- and load(), _sources() and the *_HEADER, *_SYMBOLS and *_ABI_VERSION names all come from that table.
+Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so that the environment
+library and the source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device
+raises."""
+import collections
 import ctypes
+import glob
 import os
 
 from . import _native
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
 CSRC = os.path.join(_HERE, "actor_csrc")
-HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_actor.h")
-CRITIC_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic.h")
-GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_critic_grad.h")
-OPTIM_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_optim.h")
-REPLAY_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_replay.h")
-ACTION_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_action_grad.h")
-POLICY_GRAD_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_policy_grad.h")
-LEARNER_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_learner.h")
-EXPLORE_HEADER = os.path.join(os.path.dirname(_HERE), "include", "uavx_explore.h")
 LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
-ABI_VERSION = 1
 
 SAC, TD3, DDPG = 0, 1, 2
 F32, BF16 = 0, 1
 RAW, DETERMINISTIC, SAC_SAMPLE, ADD_CLAMP = 0, 1, 2, 3
 OK, ERR_INVALID_ARG, ERR_HIP, ERR_UNSUPPORTED, ERR_NOT_PACKED = 0, -1, -2, -3, -4
 
-# every symbol include/uavx_actor.h declares (tests check the built library exports each of them)
-SYMBOLS = ("uavx_actor_version", "uavx_actor_strerror", "uavx_actor_create", "uavx_actor_destroy", "uavx_actor_pack",
-           "uavx_actor_forward")
-# every symbol include/uavx_critic.h declares
-CRITIC_SYMBOLS = ("uavx_critic_version", "uavx_critic_strerror", "uavx_critic_create", "uavx_critic_destroy",
-                  "uavx_critic_set_split_rows", "uavx_critic_pack", "uavx_critic_q", "uavx_critic_target")
-CRITIC_ABI_VERSION = 1
-SPLIT_ROWS = 16384      # UAVX_CRITIC_SPLIT_ROWS: batches below it run the small-batch variant
-# every symbol include/uavx_critic_grad.h declares
-GRAD_SYMBOLS = ("uavx_critic_grad_version", "uavx_critic_grad_workspace_bytes", "uavx_critic_grad")
-GRAD_ABI_VERSION = 1
+SPLIT_ROWS = 16384              # UAVX_CRITIC_SPLIT_ROWS: batches below it run the small-batch variant
 GRAD_MSE, GRAD_L1 = 0, 1
-GRAD_MAX_ROWS = 262144  # UAVX_CRITIC_GRAD_MAX_ROWS
-# every symbol include/uavx_optim.h declares
-OPTIM_SYMBOLS = ("uavx_optim_version", "uavx_optim_adam", "uavx_optim_soft_update")
-OPTIM_ABI_VERSION = 1
-OPTIM_MAX_TENSORS = 16  # UAVX_OPTIM_MAX_TENSORS
-# every symbol include/uavx_replay.h declares
-REPLAY_SYMBOLS = ("uavx_replay_version", "uavx_replay_workspace_bytes", "uavx_replay_sample")
-REPLAY_ABI_VERSION = 1
-REPLAY_MAX_ROWS = 1048576   # UAVX_REPLAY_MAX_ROWS
-REPLAY_SINGLE_ROWS = 1024   # UAVX_REPLAY_SINGLE_ROWS: up to here one launch and no workspace
-# every symbol include/uavx_action_grad.h declares
-ACTION_GRAD_SYMBOLS = ("uavx_action_grad_version", "uavx_action_grad")
-ACTION_GRAD_ABI_VERSION = 1
+GRAD_MAX_ROWS = 262144          # UAVX_CRITIC_GRAD_MAX_ROWS
+OPTIM_MAX_TENSORS = 16          # UAVX_OPTIM_MAX_TENSORS
+REPLAY_MAX_ROWS = 1048576       # UAVX_REPLAY_MAX_ROWS
+REPLAY_SINGLE_ROWS = 1024       # UAVX_REPLAY_SINGLE_ROWS: up to here one launch and no workspace
 ACTION_GRAD_MAX_ROWS = 262144   # UAVX_ACTION_GRAD_MAX_ROWS
-# every symbol include/uavx_policy_grad.h declares
-POLICY_GRAD_SYMBOLS = ("uavx_policy_grad_version", "uavx_policy_grad_workspace_bytes", "uavx_policy_grad_forward",
-                       "uavx_policy_grad_backward")
-POLICY_GRAD_ABI_VERSION = 1
 POLICY_GRAD_MAX_ROWS = 262144   # UAVX_POLICY_GRAD_MAX_ROWS
-# every symbol include/uavx_learner.h declares
-LEARNER_SYMBOLS = ("uavx_learner_version", "uavx_learner_tail")
-LEARNER_ABI_VERSION = 1
 LEARNER_LOG_COLUMNS = 8         # UAVX_LEARNER_LOG_COLUMNS
-# every symbol include/uavx_explore.h declares
-EXPLORE_SYMBOLS = ("uavx_explore_version", "uavx_explore_act")
-EXPLORE_ABI_VERSION = 1
 EXPLORE_MAX_ROWS = 16777216     # UAVX_EXPLORE_MAX_ROWS
 EXPLORE_STATE_BYTES = 16        # UAVX_EXPLORE_STATE_BYTES
 
@@ -91,11 +55,80 @@ class ExploreArgs(ctypes.Structure):
                 ("ou_x_initial", ctypes.c_double)]
 
 
+_vp, _i64, _i32, _f32, _f64, _str = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double,
+                                 ctypes.c_char_p)
+_pvp, _pi64 = ctypes.POINTER(_vp), ctypes.POINTER(_i64)
+
+# word: the unit's name in the ABI-mismatch message; version: the function that returns the ABI version the library speaks;
+# abi: the version this package binds; functions: every symbol the header declares (tests check the built library exports
+# each of them) -> (restype, argtypes)
+Unit = collections.namedtuple("Unit", "word header version abi functions")
+
+
+def _unit(word, header, abi, functions):
+    return Unit(word, os.path.join(_INCLUDE, header), next(iter(functions)), abi, functions)
+
+
+UNITS = (
+    _unit("actor", "uavx_actor.h", 1, {
+        "uavx_actor_version": (_i32, []),
+        "uavx_actor_strerror": (_str, [_i32]),
+        "uavx_actor_create": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _pvp]),
+        "uavx_actor_destroy": (_i32, [_vp]),
+        "uavx_actor_pack": (_i32, [_vp] + [_vp] * 8 + [_vp]),
+        "uavx_actor_forward": (_i32, [_vp, _vp, _i64, _i64, _vp, _f32, _i32, _vp, _i64, _vp])}),
+    _unit("critic", "uavx_critic.h", 1, {
+        "uavx_critic_version": (_i32, []),
+        "uavx_critic_strerror": (_str, [_i32]),
+        "uavx_critic_create": (_i32, [_i32, _i32, _i32, _i32, _i32, _i32, _pvp]),
+        "uavx_critic_destroy": (_i32, [_vp]),
+        "uavx_critic_set_split_rows": (_i32, [_vp, _i64]),
+        "uavx_critic_pack": (_i32, [_vp] + [_vp] * 12 + [_vp]),
+        "uavx_critic_q": (_i32, [_vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp]),
+        "uavx_critic_target": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _f32, _f32, _f32, _vp,
+                                      _i64, _vp, _i64, _vp])}),
+    _unit("critic-gradient", "uavx_critic_grad.h", 1, {
+        "uavx_critic_grad_version": (_i32, []),
+        "uavx_critic_grad_workspace_bytes": (_i32, [_vp, _i64, _pi64]),
+        "uavx_critic_grad": (_i32, [_vp, _i32, _pvp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _pvp, _vp, _vp, _i64, _vp])}),
+    _unit("optimiser", "uavx_optim.h", 1, {
+        "uavx_optim_version": (_i32, []),
+        "uavx_optim_adam": (_i32, [_i32, _pvp, _pvp, _pvp, _pvp, _pvp, _pvp, _pi64, _f64, _f64, _f64, _f64, _f64, _vp,
+                                   _vp, _vp]),
+        "uavx_optim_soft_update": (_i32, [_i32, _pvp, _pvp, _pi64, _f64, _vp])}),
+    _unit("replay", "uavx_replay.h", 1, {
+        "uavx_replay_version": (_i32, []),
+        "uavx_replay_workspace_bytes": (_i32, [_i64, _pi64]),
+        "uavx_replay_sample": (_i32, [ctypes.POINTER(ReplayRing), _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                      _vp, _vp, _i64, _vp])}),
+    _unit("action-gradient", "uavx_action_grad.h", 1, {
+        "uavx_action_grad_version": (_i32, []),
+        "uavx_action_grad": (_i32, [_vp, _i32, _pvp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp])}),
+    _unit("policy-gradient", "uavx_policy_grad.h", 1, {
+        "uavx_policy_grad_version": (_i32, []),
+        "uavx_policy_grad_workspace_bytes": (_i32, [_i32, _i32, _i32, _i64, _pi64]),
+        "uavx_policy_grad_forward": (_i32, [_i32, _i32, _i32, _pvp, _vp, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp]),
+        "uavx_policy_grad_backward": (_i32, [_i32, _i32, _i32, _pvp, _vp, _i64, _i64, _vp, _vp, _i64, _f32, _vp, _pvp,
+                                             _vp, _vp, _vp, _i64, _vp])}),
+    _unit("learner", "uavx_learner.h", 1, {
+        "uavx_learner_version": (_i32, []),
+        "uavx_learner_tail": (_i32, [_i32, _pvp, _vp, _f32, _vp, _vp, _vp, _vp, _f64, _f64, _f64, _f64, _vp, _vp, _i64,
+                                     _vp, _i32, _vp])}),
+    _unit("exploration", "uavx_explore.h", 1, {
+        "uavx_explore_version": (_i32, []),
+        "uavx_explore_act": (_i32, [ctypes.POINTER(ExploreArgs), _vp])}),
+)
+(HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER, POLICY_GRAD_HEADER, LEARNER_HEADER,
+ EXPLORE_HEADER) = (u.header for u in UNITS)
+(SYMBOLS, CRITIC_SYMBOLS, GRAD_SYMBOLS, OPTIM_SYMBOLS, REPLAY_SYMBOLS, ACTION_GRAD_SYMBOLS, POLICY_GRAD_SYMBOLS,
+ LEARNER_SYMBOLS, EXPLORE_SYMBOLS) = (tuple(u.functions) for u in UNITS)
+(ABI_VERSION, CRITIC_ABI_VERSION, GRAD_ABI_VERSION, OPTIM_ABI_VERSION, REPLAY_ABI_VERSION, ACTION_GRAD_ABI_VERSION,
+ POLICY_GRAD_ABI_VERSION, LEARNER_ABI_VERSION, EXPLORE_ABI_VERSION) = (u.abi for u in UNITS)
+
+
 def _sources():
-    import glob
     return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-            + [HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER,
-               POLICY_GRAD_HEADER, LEARNER_HEADER, EXPLORE_HEADER])
+            + [u.header for u in UNITS])
 
 
 def source_hash():
@@ -121,71 +154,13 @@ def load():
     if not os.path.exists(LIB_PATH) or not _up_to_date():
         build()                 # a build, not a fallback: a compile error is raised as such
     L = ctypes.CDLL(LIB_PATH)
-    vp, i64, i32, f32 = ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float
-    L.uavx_actor_version.restype = i32
-    if L.uavx_actor_version() != ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks actor ABI version {L.uavx_actor_version()}, this package binds {ABI_VERSION}: "
-                           f"rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_actor_strerror.restype = ctypes.c_char_p
-    L.uavx_actor_strerror.argtypes = [i32]
-    L.uavx_actor_create.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
-    L.uavx_actor_destroy.argtypes = [vp]
-    L.uavx_actor_pack.argtypes = [vp] + [vp] * 8 + [vp]
-    L.uavx_actor_forward.argtypes = [vp, vp, i64, i64, vp, f32, i32, vp, i64, vp]
-    L.uavx_critic_version.restype = i32
-    if L.uavx_critic_version() != CRITIC_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks critic ABI version {L.uavx_critic_version()}, this package binds "
-                           f"{CRITIC_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_critic_strerror.restype = ctypes.c_char_p
-    L.uavx_critic_strerror.argtypes = [i32]
-    L.uavx_critic_create.argtypes = [i32, i32, i32, i32, i32, i32, ctypes.POINTER(vp)]
-    L.uavx_critic_destroy.argtypes = [vp]
-    L.uavx_critic_set_split_rows.argtypes = [vp, i64]
-    L.uavx_critic_pack.argtypes = [vp] + [vp] * 12 + [vp]
-    L.uavx_critic_q.argtypes = [vp, vp, i64, i64, vp, i64, vp, i64, vp]
-    L.uavx_critic_target.argtypes = [vp, vp, vp, i64, i64, vp, i64, vp, i64, vp, vp, f32, f32, f32, vp, i64, vp, i64, vp]
-    L.uavx_critic_grad_version.restype = i32
-    if L.uavx_critic_grad_version() != GRAD_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks critic-gradient ABI version {L.uavx_critic_grad_version()}, this package "
-                           f"binds {GRAD_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_critic_grad_workspace_bytes.argtypes = [vp, i64, ctypes.POINTER(i64)]
-    L.uavx_critic_grad.argtypes = [vp, i32, ctypes.POINTER(vp), vp, i64, i64, vp, i64, vp, i64, ctypes.POINTER(vp), vp, vp,
-                                   i64, vp]
-    L.uavx_optim_version.restype = i32
-    if L.uavx_optim_version() != OPTIM_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks optimiser ABI version {L.uavx_optim_version()}, this package binds "
-                           f"{OPTIM_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    f64, pvp, pi64 = ctypes.c_double, ctypes.POINTER(vp), ctypes.POINTER(i64)
-    L.uavx_optim_adam.argtypes = [i32, pvp, pvp, pvp, pvp, pvp, pvp, pi64, f64, f64, f64, f64, f64, vp, vp, vp]
-    L.uavx_optim_soft_update.argtypes = [i32, pvp, pvp, pi64, f64, vp]
-    L.uavx_replay_version.restype = i32
-    if L.uavx_replay_version() != REPLAY_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks replay ABI version {L.uavx_replay_version()}, this package binds "
-                           f"{REPLAY_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_replay_workspace_bytes.argtypes = [i64, pi64]
-    L.uavx_replay_sample.argtypes = [ctypes.POINTER(ReplayRing), i64, vp, vp, i64, vp, vp, vp, vp, vp, vp, vp, vp, i64, vp]
-    L.uavx_action_grad_version.restype = i32
-    if L.uavx_action_grad_version() != ACTION_GRAD_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks action-gradient ABI version {L.uavx_action_grad_version()}, this package "
-                           f"binds {ACTION_GRAD_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_action_grad.argtypes = [vp, i32, pvp, vp, i64, i64, vp, i64, vp, vp, vp]
-    L.uavx_policy_grad_version.restype = i32
-    if L.uavx_policy_grad_version() != POLICY_GRAD_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks policy-gradient ABI version {L.uavx_policy_grad_version()}, this package "
-                           f"binds {POLICY_GRAD_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_policy_grad_workspace_bytes.argtypes = [i32, i32, i32, i64, pi64]
-    L.uavx_policy_grad_forward.argtypes = [i32, i32, i32, pvp, vp, i64, i64, vp, vp, vp, vp, i64, vp]
-    L.uavx_policy_grad_backward.argtypes = [i32, i32, i32, pvp, vp, i64, i64, vp, vp, i64, f32, vp, pvp, vp, vp, vp, i64, vp]
-    L.uavx_learner_version.restype = i32
-    if L.uavx_learner_version() != LEARNER_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks learner ABI version {L.uavx_learner_version()}, this package binds "
-                           f"{LEARNER_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_learner_tail.argtypes = [i32, pvp, vp, f32, vp, vp, vp, vp, f64, f64, f64, f64, vp, vp, i64, vp, i32, vp]
-    L.uavx_explore_version.restype = i32
-    if L.uavx_explore_version() != EXPLORE_ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks exploration ABI version {L.uavx_explore_version()}, this package binds "
-                           f"{EXPLORE_ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    L.uavx_explore_act.argtypes = [ctypes.POINTER(ExploreArgs), vp]
+    for u in UNITS:
+        for name, (restype, argtypes) in u.functions.items():       # the version function comes first
+            f = getattr(L, name)
+            f.restype, f.argtypes = restype, argtypes
+            if name == u.version and f() != u.abi:
+                raise RuntimeError(f"{LIB_PATH} speaks {u.word} ABI version {f()}, this package binds {u.abi}: "
+                                   f"rebuild it (`make -B -C {CSRC}`)")
     _lib_handle = L
     return L
 

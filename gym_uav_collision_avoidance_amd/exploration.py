@@ -17,6 +17,7 @@ import math
 import torch
 
 from . import _actor_lib
+from ._fused_common import stream
 
 
 def launch(lib, stream, **fields):
@@ -148,7 +149,7 @@ class Exploration:
         if flags is not None:
             fields.update(reset_flags=flags[0], reset_stride=flags[1], reset_mask=flags[2], rows_per_env=flags[3])
         a._launch(o2, None, 0.0, _actor_lib.RAW, self._raw, self._cols)
-        rc = launch(self._lib, a._stream(), kind=self.kind, rows=self.rows, row_offset=self.row_offset, seed=self.seed,
+        rc = launch(self._lib, stream(self.device), kind=self.kind, rows=self.rows, row_offset=self.row_offset, seed=self.seed,
                     raw=self._raw.data_ptr(), raw_stride=self._cols, out=d2.data_ptr(),
                     out_stride=d2.stride(0) if self.rows > 1 else 2, state=self.state.data_ptr(),
                     warmup_steps=self.warmup_steps, random_prob_dev=self._prob.data_ptr(), random_prob=self.random_prob,

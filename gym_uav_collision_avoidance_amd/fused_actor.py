@@ -13,38 +13,24 @@ import ctypes
 import torch
 
 from . import _actor_lib
-from .policy import DDPGActor, GaussianPolicy, TD3Actor
-
-_PRECISIONS = {"f32": _actor_lib.F32, "bf16": _actor_lib.BF16}
+from ._fused_common import PRECISIONS, actor_layers, check_packable, pack_pointers, stream
 
 
 class FusedActor:
     def __init__(self, module, precision="f32"):
-        if isinstance(module, GaussianPolicy):
-            kind, layers = _actor_lib.SAC, (module.linear1, module.linear2, module.mean_linear, module.log_std_linear)
-        elif isinstance(module, TD3Actor):
-            kind, layers = _actor_lib.TD3, (module.l1, module.l2, module.l3)
-        elif isinstance(module, DDPGActor):
-            kind, layers = _actor_lib.DDPG, (module.input, module.fc1, module.fc2)
-        else:
+        found = actor_layers(module)
+        if found is None:
             raise TypeError(f"uavx: FusedActor takes a GaussianPolicy, TD3Actor or DDPGActor, not {type(module).__name__}")
-        if precision not in _PRECISIONS:
-            raise ValueError(f"uavx: precision must be one of {sorted(_PRECISIONS)}, not {precision!r}")
-        w = layers[0].weight
-        if w.device.type != "cuda":
-            raise ValueError(f"uavx: FusedActor needs the module on a GPU (cuda:N), its parameters are on {w.device}")
-        for lin in layers:
-            if lin.weight.dtype != torch.float32 or lin.bias is None or lin.bias.dtype != torch.float32:
-                raise TypeError("uavx: FusedActor packs float32 parameters; keep the module in float32 and pick "
-                                "precision='bf16' for the bf16 kernel")
-        self.module, self.kind, self.precision, self.device = module, kind, precision, w.device
+        kind, layers = found
+        device = check_packable(layers, precision, "FusedActor")
+        self.module, self.kind, self.precision, self.device = module, kind, precision, device
         self._layers = layers
         self._lib = _actor_lib.load()
         self.obs_dim, self.hidden1 = layers[0].in_features, layers[0].out_features
         self.hidden2, self.act_dim = layers[1].out_features, layers[2].out_features
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            rc = self._lib.uavx_actor_create(kind, _PRECISIONS[precision], self.obs_dim, self.hidden1, self.hidden2,
+            rc = self._lib.uavx_actor_create(kind, PRECISIONS[precision], self.obs_dim, self.hidden1, self.hidden2,
                                              self.act_dim, ctypes.byref(h))
         _actor_lib.check(rc, f"uavx_actor_create({type(module).__name__}, {self.obs_dim}->{self.hidden1}->{self.hidden2}->"
                              f"{self.act_dim}, {precision})")
@@ -57,16 +43,14 @@ class FusedActor:
         return cls(module, precision)
 
     def _stream(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
+        """stream(self.device).  Not called in this tree: kept for code written against the method, such as the earlier
+        tests/test_gpu_explore.py, which has to keep passing against this package."""
+        return stream(self.device)
 
     def refresh(self):
         """Re-packs the module's current parameters (one launch on the current stream)."""
-        ps = []
-        for lin in self._layers:
-            ps += [lin.weight.detach().contiguous(), lin.bias.detach().contiguous()]
-        self._keep = ps               # stream-ordered reuse keeps them valid anyway; contiguous() copies live until here
-        ptrs = [p.data_ptr() for p in ps] + ([None, None] if len(ps) == 6 else [])
-        _actor_lib.check(self._lib.uavx_actor_pack(self._h, *ptrs, self._stream()), "uavx_actor_pack")
+        self._keep, ptrs = pack_pointers(self._layers, 8)   # contiguous() copies live until the next pack
+        _actor_lib.check(self._lib.uavx_actor_pack(self._h, *ptrs, stream(self.device)), "uavx_actor_pack")
         return self
 
     def _rows(self, obs):
@@ -100,7 +84,7 @@ class FusedActor:
         obs_stride = o2.stride(0) if rows > 1 else self.obs_dim
         out_stride = d2.stride(0) if rows > 1 else cols
         rc = self._lib.uavx_actor_forward(self._h, o2.data_ptr(), rows, obs_stride, None if eps is None else eps.data_ptr(),
-                                          float(scale), mode, d2.data_ptr(), out_stride, self._stream())
+                                          float(scale), mode, d2.data_ptr(), out_stride, stream(self.device))
         _actor_lib.check(rc, "uavx_actor_forward")
         return out
 

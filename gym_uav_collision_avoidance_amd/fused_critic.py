@@ -22,73 +22,31 @@ import ctypes
 import torch
 
 from . import _actor_lib
+from ._fused_common import (KIND_NAMES, PRECISIONS, ParamSlots, Workspace, actor_layers, alpha_arg, check_buffers,
+                            check_on_gpu, check_packable, column, critic_layers, noise_arg, pack_pointers, rows2,
+                            stream)
 from .fused_actor import FusedActor
-from .policy import DDPGActor, DDPGCritic, GaussianPolicy, TD3Actor, TD3TwinQ, TwinQ
-
-_PRECISIONS = {"f32": _actor_lib.F32, "bf16": _actor_lib.BF16}
-_KIND_NAMES = {_actor_lib.SAC: "SAC", _actor_lib.TD3: "TD3", _actor_lib.DDPG: "DDPG"}
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _check_f32(t, device, what):
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != device:
-        raise TypeError(f"uavx: {what} must be a float32 tensor on {device}, got {getattr(t, 'dtype', type(t))} on "
-                        f"{getattr(t, 'device', 'host')}")
-
-
-def _rows2(t, cols, device, what):
-    """t [B, cols] float32 on device with unit last stride -> (B, row stride)."""
-    _check_f32(t, device, what)
-    if t.dim() != 2 or t.shape[1] != cols:
-        raise ValueError(f"uavx: {what} must be [B, {cols}], got {tuple(t.shape)}")
-    if t.shape[0] and t.stride(1) != 1:
-        raise ValueError(f"uavx: {what} must have unit stride along its last dimension")
-    return t.shape[0], (t.stride(0) if t.shape[0] > 1 else cols)
-
-
-def _column(t, rows, device, what):
-    """t [B] or [B, 1] float32 on device, any row stride -> row stride."""
-    _check_f32(t, device, what)
-    if tuple(t.shape) not in ((rows,), (rows, 1)):
-        raise ValueError(f"uavx: {what} must be [{rows}] or [{rows}, 1], got {tuple(t.shape)}")
-    return t.stride(0) if rows > 1 else 1
 
 
 class FusedCritic:
     def __init__(self, module, precision="f32"):
-        if isinstance(module, TwinQ):
-            kind = _actor_lib.SAC
-            layers = (module.linear1, module.linear2, module.linear3, module.linear4, module.linear5, module.linear6)
-        elif isinstance(module, TD3TwinQ):
-            kind, layers = _actor_lib.TD3, (module.l1, module.l2, module.l3, module.l4, module.l5, module.l6)
-        elif isinstance(module, DDPGCritic):
-            kind, layers = _actor_lib.DDPG, (module.input, module.fc1, module.fc2)
-        else:
+        found = critic_layers(module)
+        if found is None:
             raise TypeError(f"uavx: FusedCritic takes a TwinQ, TD3TwinQ or DDPGCritic, not {type(module).__name__}")
-        if precision not in _PRECISIONS:
-            raise ValueError(f"uavx: precision must be one of {sorted(_PRECISIONS)}, not {precision!r}")
-        w = layers[0].weight
-        if w.device.type != "cuda":
-            raise ValueError(f"uavx: FusedCritic needs the module on a GPU (cuda:N), its parameters are on {w.device}")
-        for lin in layers:
-            if lin.weight.dtype != torch.float32 or lin.bias is None or lin.bias.dtype != torch.float32:
-                raise TypeError("uavx: FusedCritic packs float32 parameters; keep the module in float32 and pick "
-                                "precision='bf16' for the bf16 kernel")
+        kind, layers = found
+        device = check_packable(layers, precision, "FusedCritic")
         self.act_dim = 2
         self.obs_dim = layers[0].in_features - self.act_dim
         self.hidden1, self.hidden2 = layers[0].out_features, layers[1].out_features
         if len(layers) == 6 and tuple(l.weight.shape for l in layers[:3]) != tuple(l.weight.shape for l in layers[3:]):
             raise ValueError("uavx: the two towers of a twin critic must have the same shapes")
-        self.module, self.kind, self.precision, self.device = module, kind, precision, w.device
+        self.module, self.kind, self.precision, self.device = module, kind, precision, device
         self.towers = 2 if len(layers) == 6 else 1
         self._layers = layers
         self._lib = _actor_lib.load()
         h = ctypes.c_void_p()
         with torch.cuda.device(self.device):
-            rc = self._lib.uavx_critic_create(kind, _PRECISIONS[precision], self.obs_dim, self.hidden1, self.hidden2,
+            rc = self._lib.uavx_critic_create(kind, PRECISIONS[precision], self.obs_dim, self.hidden1, self.hidden2,
                                               self.act_dim, ctypes.byref(h))
         _actor_lib.check_critic(rc, f"uavx_critic_create({type(module).__name__}, {layers[0].in_features}->{self.hidden1}->"
                                     f"{self.hidden2}->1, {precision})")
@@ -102,12 +60,8 @@ class FusedCritic:
 
     def refresh(self):
         """Re-packs the module's current parameters (one launch on the current stream)."""
-        ps = []
-        for lin in self._layers:
-            ps += [lin.weight.detach().contiguous(), lin.bias.detach().contiguous()]
-        self._keep = ps
-        ptrs = [p.data_ptr() for p in ps] + [None] * (12 - len(ps))
-        _actor_lib.check_critic(self._lib.uavx_critic_pack(self._h, *ptrs, _stream(self.device)), "uavx_critic_pack")
+        self._keep, ptrs = pack_pointers(self._layers, 12)
+        _actor_lib.check_critic(self._lib.uavx_critic_pack(self._h, *ptrs, stream(self.device)), "uavx_critic_pack")
         return self
 
     def set_split_rows(self, rows):
@@ -119,20 +73,20 @@ class FusedCritic:
     def q(self, state, action, out=None):
         """(q1, q2), each [B, 1], for a twin critic, q [B, 1] for DDPG: the module's forward on [B, 10] states and [B, 2]
         actions.  out: an optional float32 [B, 2] (twin) / [B, 1] tensor written in place; the results are views of it."""
-        rows, s_stride = _rows2(state, self.obs_dim, self.device, "state")
-        arows, a_stride = _rows2(action, self.act_dim, self.device, "action")
+        rows, s_stride = rows2(state, self.obs_dim, self.device, "state")
+        arows, a_stride = rows2(action, self.act_dim, self.device, "action")
         if arows != rows:
             raise ValueError(f"uavx: state and action rows differ ({rows} vs {arows})")
         cols = self.towers
         if out is None:
             out = torch.empty((rows, cols), dtype=torch.float32, device=self.device)
         else:
-            _rows2(out, cols, self.device, "out")
+            rows2(out, cols, self.device, "out")
             if out.shape[0] != rows:
                 raise ValueError(f"uavx: out must be [{rows}, {cols}], got {tuple(out.shape)}")
         o_stride = out.stride(0) if rows > 1 else cols
         rc = self._lib.uavx_critic_q(self._h, state.data_ptr(), rows, s_stride, action.data_ptr(), a_stride, out.data_ptr(),
-                                     o_stride, _stream(self.device))
+                                     o_stride, stream(self.device))
         _actor_lib.check_critic(rc, "uavx_critic_q")
         return (out[:, 0:1], out[:, 1:2]) if cols == 2 else out
 
@@ -150,6 +104,17 @@ class FusedCritic:
             pass
 
 
+def critic_handle(critic, who):
+    """(FusedCritic, owned) for a block that takes a TwinQ / TD3TwinQ / DDPGCritic on a GPU or an open FusedCritic: the
+    handle, and whether it was built here from the module, so that the block's close() releases it."""
+    if isinstance(critic, FusedCritic):
+        return critic, False
+    if critic_layers(critic) is None:
+        raise TypeError(f"uavx: {who} takes a TwinQ, TD3TwinQ, DDPGCritic or FusedCritic, not {type(critic).__name__}")
+    check_on_gpu(next(critic.parameters()).device, who)
+    return FusedCritic.from_module(critic), True
+
+
 class FusedTarget:
     """The learner's TD target from a (next-action actor, target critic) pair: SAC (GaussianPolicy, TwinQ), TD3
     (TD3Actor, TD3TwinQ) or DDPG (DDPGActor, DDPGCritic).  actor / critic: modules or FusedActor / FusedCritic of the
@@ -164,8 +129,8 @@ class FusedTarget:
             critic = FusedCritic.from_module(critic, precision)
             self._owned.append(critic)
         if actor.kind != critic.kind:
-            raise TypeError(f"uavx: FusedTarget pairs a {_KIND_NAMES[actor.kind]} actor ({type(actor.module).__name__}) "
-                            f"with a {_KIND_NAMES[critic.kind]} critic ({type(critic.module).__name__})")
+            raise TypeError(f"uavx: FusedTarget pairs a {KIND_NAMES[actor.kind]} actor ({type(actor.module).__name__}) "
+                            f"with a {KIND_NAMES[critic.kind]} critic ({type(critic.module).__name__})")
         if actor.precision != critic.precision:
             raise ValueError(f"uavx: actor ({actor.precision}) and critic ({critic.precision}) precisions differ")
         if actor.device != critic.device:
@@ -177,7 +142,7 @@ class FusedTarget:
 
     @property
     def learner(self):
-        return _KIND_NAMES[self.kind].lower()
+        return KIND_NAMES[self.kind].lower()
 
     def refresh(self):
         """Re-packs both networks (two launches on the current stream; capturable)."""
@@ -197,15 +162,15 @@ class FusedTarget:
         `noise` ([B, 2] float32) given; out: optional [B, 1] / [B] float32 written in place; aux: optional [B, 4] float32
         receiving a'0, a'1, logπ (0 unless SAC), min Q."""
         dev = self.device
-        rows, s_stride = _rows2(next_state, self.critic.obs_dim, dev, "next_state")
-        r_stride = _column(reward, rows, dev, "reward")
-        m_stride = _column(mask, rows, dev, "mask")
+        rows, s_stride = rows2(next_state, self.critic.obs_dim, dev, "next_state")
+        r_stride = column(reward, rows, dev, "reward")
+        m_stride = column(mask, rows, dev, "mask")
         if out is None:
             out = torch.empty((rows, 1), dtype=torch.float32, device=dev)
-        o_stride = _column(out, rows, dev, "out")
+        o_stride = column(out, rows, dev, "out")
         a_ptr, a_stride = None, 4
         if aux is not None:
-            arows, a_stride = _rows2(aux, 4, dev, "aux")
+            arows, a_stride = rows2(aux, 4, dev, "aux")
             if arows != rows:
                 raise ValueError(f"uavx: aux must be [{rows}, 4], got {tuple(aux.shape)}")
             a_ptr = aux.data_ptr()
@@ -214,18 +179,13 @@ class FusedTarget:
             if noise is None:
                 noise = torch.randn((rows, 2), generator=generator, device=dev, dtype=torch.float32)
             else:
-                nrows, _ = _rows2(noise, 2, dev, "noise")
+                nrows, _ = rows2(noise, 2, dev, "noise")
                 if nrows != rows or (rows > 1 and noise.stride(0) != 2):
                     raise ValueError(f"uavx: noise must be a contiguous [{rows}, 2] tensor")
             eps_ptr = noise.data_ptr()
         alpha_ptr = None
         if self.kind == _actor_lib.SAC:
-            if alpha is None:
-                raise ValueError("uavx: a SAC target needs alpha (a float or a 1-element float32 device tensor)")
-            if torch.is_tensor(alpha):
-                _check_f32(alpha, dev, "alpha")
-                if alpha.numel() != 1:
-                    raise ValueError(f"uavx: alpha must have one element, got {tuple(alpha.shape)}")
+            if alpha_arg(alpha, dev, "target"):
                 alpha_ptr = alpha.data_ptr()
             else:
                 self._alpha.fill_(float(alpha))
@@ -234,7 +194,7 @@ class FusedTarget:
         rc = self.critic._lib.uavx_critic_target(
             self.critic._h, self.actor._h, next_state.data_ptr(), rows, s_stride, reward.data_ptr(), r_stride,
             mask.data_ptr(), m_stride, eps_ptr, alpha_ptr, self.gamma, self.policy_noise, self.noise_clip, out.data_ptr(),
-            o_stride, a_ptr, a_stride, _stream(dev))
+            o_stride, a_ptr, a_stride, stream(dev))
         _actor_lib.check_critic(rc, "uavx_critic_target")
         return out
 
@@ -263,36 +223,20 @@ class FusedCriticLoss:
     snapshot of a FusedCritic untouched.  Inputs must be float32 on the module's device; anything else raises."""
 
     def __init__(self, critic, loss=None):
-        if isinstance(critic, FusedCritic):
-            fc, self._owned = critic, None
-        elif isinstance(critic, (TwinQ, TD3TwinQ, DDPGCritic)):
-            fc = None
-        else:
-            raise TypeError(f"uavx: FusedCriticLoss takes a TwinQ, TD3TwinQ, DDPGCritic or FusedCritic, not "
-                            f"{type(critic).__name__}")
-        module = fc.module if fc is not None else critic
-        kind = (_actor_lib.SAC if isinstance(module, TwinQ) else _actor_lib.TD3 if isinstance(module, TD3TwinQ)
-                else _actor_lib.DDPG)
-        if loss is None:
-            loss = _DEFAULT_LOSS[kind]
-        if loss not in _LOSSES:
-            raise ValueError(f"uavx: loss must be one of {sorted(_LOSSES)} or None, not {loss!r}")
-        if fc is None:
-            w = next(module.parameters())
-            if w.device.type != "cuda":
-                raise ValueError(f"uavx: FusedCriticLoss needs the module on a GPU (cuda:N), its parameters are on {w.device}")
-            fc = FusedCritic.from_module(module)
-            self._owned = fc
-        self.critic, self.module, self.kind, self.device = fc, module, fc.kind, fc.device
+        # the loss is checked behind the critic's type and before its device, on the host
+        found = critic_layers(critic.module if isinstance(critic, FusedCritic) else critic)
+        if found is not None:
+            loss = _DEFAULT_LOSS[found[0]] if loss is None else loss
+            if loss not in _LOSSES:
+                raise ValueError(f"uavx: loss must be one of {sorted(_LOSSES)} or None, not {loss!r}")
+        fc, owned = critic_handle(critic, "FusedCriticLoss")
+        self._owned = fc if owned else None
+        self.critic, self.module, self.kind, self.device = fc, fc.module, fc.kind, fc.device
         self.loss = loss
         self._lib = fc._lib
-        self._params = [p for lin in fc._layers for p in (lin.weight, lin.bias)]
-        # persistent .grad buffers, assigned to a parameter whose .grad is missing or unusable (no allocation per call)
-        self._gbuf = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in self._params]
+        self._slots = ParamSlots((p for lin in fc._layers for p in (lin.weight, lin.bias)), 12, "FusedCriticLoss", "critic")
         self._loss = torch.zeros(fc.towers, dtype=torch.float32, device=self.device)
-        self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
-        self._gptrs = (ctypes.c_void_p * 12)()
-        self._pptrs = (ctypes.c_void_p * 12)()
+        self._ws = Workspace(self.device)
 
     def workspace_bytes(self, rows):
         n = ctypes.c_int64()
@@ -302,49 +246,27 @@ class FusedCriticLoss:
 
     def reserve(self, rows):
         """Grows the workspace to what `rows` rows need (a graph capture cannot allocate it)."""
-        need = self.workspace_bytes(rows)
-        if self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws.reserve(self.workspace_bytes(rows))
         return self
-
-    def _grads(self):
-        out = []
-        for p, buf in zip(self._params, self._gbuf):
-            g = p.grad
-            if (g is None or g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape
-                    or not g.is_contiguous()):
-                p.grad = g = buf
-            out.append(g)
-        return out
 
     def backward(self, state, action, y):
         """Overwrites every critic parameter's .grad with the gradient of the loss on [B, 10] states, [B, 2] actions
         (any row stride) and targets y ([B] or [B, 1], any stride); returns the loss of each tower as 0-d device tensors
         (l1, l2), or the one loss of a DDPG critic."""
         dev = self.device
-        rows, s_stride = _rows2(state, self.critic.obs_dim, dev, "state")
-        arows, a_stride = _rows2(action, self.critic.act_dim, dev, "action")
+        rows, s_stride = rows2(state, self.critic.obs_dim, dev, "state")
+        arows, a_stride = rows2(action, self.critic.act_dim, dev, "action")
         if arows != rows:
             raise ValueError(f"uavx: state and action rows differ ({rows} vs {arows})")
-        y_stride = _column(y, rows, dev, "y")
+        y_stride = column(y, rows, dev, "y")
         if rows < 1 or rows > _actor_lib.GRAD_MAX_ROWS:
             raise ValueError(f"uavx: FusedCriticLoss takes 1..{_actor_lib.GRAD_MAX_ROWS} rows, got {rows}")
-        for p in self._params:
-            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
-                raise TypeError("uavx: FusedCriticLoss reads contiguous float32 parameters on the critic's device")
-        need = self.workspace_bytes(rows)
-        if self._ws.numel() < need:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"uavx: the workspace for {rows} rows must exist before a graph capture: call "
-                                   f"reserve({rows}) first")
-            self.reserve(rows)
-        grads = self._grads()
-        for i, (p, g) in enumerate(zip(self._params, grads)):
-            self._pptrs[i] = p.data_ptr()
-            self._gptrs[i] = g.data_ptr()
-        rc = self._lib.uavx_critic_grad(self.critic._h, _LOSSES[self.loss], self._pptrs, state.data_ptr(), rows, s_stride,
-                                        action.data_ptr(), a_stride, y.data_ptr(), y_stride, self._gptrs,
-                                        self._loss.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _stream(dev))
+        pptrs = self._slots.fill_params(dev)
+        self._ws.ensure(self.workspace_bytes(rows), rows)
+        ws = self._ws.buf
+        rc = self._lib.uavx_critic_grad(self.critic._h, _LOSSES[self.loss], pptrs, state.data_ptr(), rows, s_stride,
+                                        action.data_ptr(), a_stride, y.data_ptr(), y_stride, self._slots.fill_grads(),
+                                        self._loss.data_ptr(), ws.data_ptr(), ws.numel(), stream(dev))
         _actor_lib.check_critic(rc, "uavx_critic_grad")
         return (self._loss[0], self._loss[1]) if self.critic.towers == 2 else self._loss[0]
 
@@ -393,23 +315,12 @@ class FusedActionGrad:
     the critic's parameters and `state` receive no gradient and their .grad is not touched."""
 
     def __init__(self, critic):
-        if isinstance(critic, FusedCritic):
-            fc, self._owned = critic, None
-        elif isinstance(critic, (TwinQ, TD3TwinQ, DDPGCritic)):
-            fc = None
-        else:
-            raise TypeError(f"uavx: FusedActionGrad takes a TwinQ, TD3TwinQ, DDPGCritic or FusedCritic, not "
-                            f"{type(critic).__name__}")
-        if fc is None:
-            w = next(critic.parameters())
-            if w.device.type != "cuda":
-                raise ValueError(f"uavx: FusedActionGrad needs the module on a GPU (cuda:N), its parameters are on {w.device}")
-            fc = FusedCritic.from_module(critic)
-            self._owned = fc
+        fc, owned = critic_handle(critic, "FusedActionGrad")
+        self._owned = fc if owned else None
         self.critic, self.module, self.kind, self.device = fc, fc.module, fc.kind, fc.device
         self._lib = fc._lib
-        self._params = [p for lin in fc._layers for p in (lin.weight, lin.bias)]
-        self._pptrs = (ctypes.c_void_p * 12)()
+        self._slots = ParamSlots((p for lin in fc._layers for p in (lin.weight, lin.bias)), 12, "FusedActionGrad", "critic",
+                                 grads=False)
 
     def _mask(self, towers):
         full = (1 << self.critic.towers) - 1
@@ -418,7 +329,7 @@ class FusedActionGrad:
         if isinstance(towers, bool) or not isinstance(towers, int):
             raise TypeError(f"uavx: towers must be an int bit mask or None, not {type(towers).__name__}")
         if towers < 1 or towers & ~full:
-            raise ValueError(f"uavx: towers mask {towers} selects nothing or a tower this {_KIND_NAMES[self.kind]} critic "
+            raise ValueError(f"uavx: towers mask {towers} selects nothing or a tower this {KIND_NAMES[self.kind]} critic "
                              f"({self.critic.towers} tower(s)) does not have")
         return towers
 
@@ -429,28 +340,21 @@ class FusedActionGrad:
         uninitialised).  out = (q, dqda): preallocated contiguous float32 buffers, e.g. for a graph capture."""
         dev, T = self.device, self.critic.towers
         mask = self._mask(towers)
-        rows, s_stride = _rows2(state, self.critic.obs_dim, dev, "state")
-        arows, a_stride = _rows2(action, self.critic.act_dim, dev, "action")
+        rows, s_stride = rows2(state, self.critic.obs_dim, dev, "state")
+        arows, a_stride = rows2(action, self.critic.act_dim, dev, "action")
         if arows != rows:
             raise ValueError(f"uavx: state and action rows differ ({rows} vs {arows})")
         if rows < 1 or rows > _actor_lib.ACTION_GRAD_MAX_ROWS:
             raise ValueError(f"uavx: FusedActionGrad takes 1..{_actor_lib.ACTION_GRAD_MAX_ROWS} rows, got {rows}")
-        for p in self._params:
-            if p.dtype != torch.float32 or p.device != dev or not p.is_contiguous():
-                raise TypeError("uavx: FusedActionGrad reads contiguous float32 parameters on the critic's device")
+        pptrs = self._slots.fill_params(dev)
         if out is None:
             q = torch.empty((T, rows), dtype=torch.float32, device=dev)
             j = torch.empty((T, rows, 2), dtype=torch.float32, device=dev)
         else:
             q, j = out
-            for t, shape, what in ((q, (T, rows), "out[0]"), (j, (T, rows, 2), "out[1]")):
-                _check_f32(t, dev, what)
-                if tuple(t.shape) != shape or not t.is_contiguous():
-                    raise ValueError(f"uavx: {what} must be a contiguous {list(shape)} tensor, got {tuple(t.shape)}")
-        for i, p in enumerate(self._params):
-            self._pptrs[i] = p.data_ptr()
-        rc = self._lib.uavx_action_grad(self.critic._h, mask, self._pptrs, state.data_ptr(), rows, s_stride,
-                                        action.data_ptr(), a_stride, q.data_ptr(), j.data_ptr(), _stream(dev))
+            check_buffers(((q, (T, rows), "out[0]"), (j, (T, rows, 2), "out[1]")), dev)
+        rc = self._lib.uavx_action_grad(self.critic._h, mask, pptrs, state.data_ptr(), rows, s_stride,
+                                        action.data_ptr(), a_stride, q.data_ptr(), j.data_ptr(), stream(dev))
         _actor_lib.check_critic(rc, "uavx_action_grad")
         return q, j
 
@@ -465,9 +369,6 @@ class FusedActionGrad:
         if self._owned is not None:
             self._owned.close()
             self._owned = None
-
-
-_ACTOR_KINDS = ((GaussianPolicy, _actor_lib.SAC), (TD3Actor, _actor_lib.TD3), (DDPGActor, _actor_lib.DDPG))
 
 
 class FusedActorLoss:
@@ -486,15 +387,16 @@ class FusedActorLoss:
     a FusedActionGrad."""
 
     def __init__(self, actor, critic):
-        kind = next((k for cls, k in _ACTOR_KINDS if isinstance(actor, cls)), None)
-        if kind is None:
+        found = actor_layers(actor)
+        if found is None:
             raise TypeError(f"uavx: FusedActorLoss takes a GaussianPolicy, TD3Actor or DDPGActor, not {type(actor).__name__}")
+        kind = found[0]
         self._owned = None
         if not isinstance(critic, FusedActionGrad):
             critic = self._owned = FusedActionGrad(critic)
         if critic.kind != kind:
-            raise TypeError(f"uavx: FusedActorLoss pairs a {_KIND_NAMES[kind]} actor ({type(actor).__name__}) with a "
-                            f"{_KIND_NAMES[critic.kind]} critic ({type(critic.module).__name__})")
+            raise TypeError(f"uavx: FusedActorLoss pairs a {KIND_NAMES[kind]} actor ({type(actor).__name__}) with a "
+                            f"{KIND_NAMES[critic.kind]} critic ({type(critic.module).__name__})")
         params = list(actor.parameters())
         for p in params:
             if p.device != critic.device or p.dtype != torch.float32:
@@ -505,7 +407,7 @@ class FusedActorLoss:
 
     @property
     def learner(self):
-        return _KIND_NAMES[self.kind].lower()
+        return KIND_NAMES[self.kind].lower()
 
     def backward(self, state, alpha=None, noise=None, generator=None):
         """Sets every actor parameter's .grad to the gradient of the actor loss on `state` [B, 10] (cleared first, not
@@ -513,20 +415,12 @@ class FusedActorLoss:
         alpha update (sac.py:82) needs no second forward.  SAC: alpha is a float or a device tensor; eps is `noise`
         ([B, 2]) or torch.randn((B, 2), generator=generator)."""
         dev = self.device
-        rows, _ = _rows2(state, self.critic.critic.obs_dim, dev, "state")
+        rows, _ = rows2(state, self.critic.critic.obs_dim, dev, "state")
         if rows < 1 or rows > _actor_lib.ACTION_GRAD_MAX_ROWS:
             raise ValueError(f"uavx: FusedActorLoss takes 1..{_actor_lib.ACTION_GRAD_MAX_ROWS} rows, got {rows}")
         if self.kind == _actor_lib.SAC:
-            if alpha is None:
-                raise ValueError("uavx: a SAC actor loss needs alpha (a float or a device tensor)")
-            if torch.is_tensor(alpha):
-                _check_f32(alpha, dev, "alpha")
-            if noise is None:
-                noise = torch.randn((rows, 2), generator=generator, device=dev, dtype=torch.float32)
-            else:
-                _check_f32(noise, dev, "noise")
-                if tuple(noise.shape) != (rows, 2):
-                    raise ValueError(f"uavx: noise must be [{rows}, 2], got {tuple(noise.shape)}")
+            alpha_arg(alpha, dev, "actor loss", one_element=False)
+            noise = noise_arg(noise, rows, dev, generator, contiguous=False)
         for p in self._params:
             p.grad = None
         with torch.enable_grad():

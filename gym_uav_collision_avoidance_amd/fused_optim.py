@@ -20,14 +20,11 @@ import ctypes
 import torch
 
 from . import _actor_lib
+from ._fused_common import stream
 from .fused_actor import FusedActor
 from .fused_critic import FusedCritic, FusedTarget
 
 _MAXT = _actor_lib.OPTIM_MAX_TENSORS
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def _params_of(x, what):
@@ -108,7 +105,7 @@ def soft_update(target, source, tau):
             for i, t in enumerate(ts[k:k + _MAXT]):
                 tab.numel[i] = t.numel()
             rc = lib.uavx_optim_soft_update(tab.n, tab.fill("t", ts[k:k + _MAXT]), tab.fill("s", ss[k:k + _MAXT]), tab.numel,
-                                            tau, _stream(dev))
+                                            tau, stream(dev))
             _actor_lib.check(rc, "uavx_optim_soft_update")
 
 
@@ -273,11 +270,11 @@ class FusedAdam:
                           tab.fill("m", [s["exp_avg"] for s in sts]), tab.fill("v", [s["exp_avg_sq"] for s in sts]),
                           tab.fill("x", [s["max_exp_avg_sq"] for s in sts]) if g["amsgrad"] else None,
                           tab.fill("t", self._targets[gi]) if update_target else None))
-        stream = _stream(dev)
+        st = stream(dev)
         with torch.cuda.device(dev):
             for gi, tab, (lr, b1, b2, eps), p, g, m, v, x, t in calls:
                 rc = self._lib.uavx_optim_adam(tab.n, p, g, m, v, x, t, tab.numel, lr, b1, b2, eps, self.tau,
-                                               self._step_ptr + 8 * gi, self._scalar_ptr + 8 * gi, stream)
+                                               self._step_ptr + 8 * gi, self._scalar_ptr + 8 * gi, st)
                 _actor_lib.check(rc, "uavx_optim_adam")
         if refresh is not None:
             refresh.refresh()

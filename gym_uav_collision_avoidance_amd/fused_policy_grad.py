@@ -22,18 +22,9 @@ import ctypes
 import torch
 
 from . import _actor_lib
-from .fused_critic import _ACTOR_KINDS, _KIND_NAMES, FusedActionGrad, FusedCritic, _check_f32, _rows2, _stream
-from .policy import DDPGCritic, TD3TwinQ, TwinQ
-
-_CRITIC_KINDS = ((TwinQ, _actor_lib.SAC), (TD3TwinQ, _actor_lib.TD3), (DDPGCritic, _actor_lib.DDPG))
-
-
-def _layers(actor, kind):
-    if kind == _actor_lib.SAC:
-        return (actor.linear1, actor.linear2, actor.mean_linear, actor.log_std_linear)
-    if kind == _actor_lib.TD3:
-        return (actor.l1, actor.l2, actor.l3)
-    return (actor.input, actor.fc1, actor.fc2)
+from ._fused_common import (KIND_NAMES, ParamSlots, Workspace, actor_layers, alpha_arg, capture_guard, check_buffers,
+                            check_on_gpu, critic_layers, noise_arg, rows2, stream)
+from .fused_critic import FusedActionGrad, FusedCritic
 
 
 class FusedPolicyGrad:
@@ -43,22 +34,20 @@ class FusedPolicyGrad:
     parameters' .grad is not touched."""
 
     def __init__(self, actor, critic):
-        kind = next((k for cls, k in _ACTOR_KINDS if isinstance(actor, cls)), None)
-        if kind is None:
+        found = actor_layers(actor)
+        if found is None:
             raise TypeError(f"uavx: FusedPolicyGrad takes a GaussianPolicy, TD3Actor or DDPGActor, not {type(actor).__name__}")
         # the pair and the devices are checked on the host, before anything touches a device
         cmod = critic.module if isinstance(critic, (FusedActionGrad, FusedCritic)) else critic
-        ckind = next((k for cls, k in _CRITIC_KINDS if isinstance(cmod, cls)), None)
-        if ckind is None:
+        cfound = critic_layers(cmod)
+        if cfound is None:
             raise TypeError(f"uavx: FusedPolicyGrad takes a TwinQ, TD3TwinQ, DDPGCritic, FusedCritic or FusedActionGrad as "
                             f"its critic, not {type(critic).__name__}")
+        (kind, layers), ckind = found, cfound[0]
         if ckind != kind:
-            raise TypeError(f"uavx: FusedPolicyGrad pairs a {_KIND_NAMES[kind]} actor ({type(actor).__name__}) with a "
-                            f"{_KIND_NAMES[ckind]} critic ({type(cmod).__name__})")
-        layers = _layers(actor, kind)
-        w = layers[0].weight
-        if w.device.type != "cuda":
-            raise ValueError(f"uavx: FusedPolicyGrad needs the actor on a GPU (cuda:N), its parameters are on {w.device}")
+            raise TypeError(f"uavx: FusedPolicyGrad pairs a {KIND_NAMES[kind]} actor ({type(actor).__name__}) with a "
+                            f"{KIND_NAMES[ckind]} critic ({type(cmod).__name__})")
+        check_on_gpu(layers[0].weight.device, "FusedPolicyGrad", "actor")
         self._owned = None
         if not isinstance(critic, FusedActionGrad):
             critic = self._owned = FusedActionGrad(critic)
@@ -71,26 +60,22 @@ class FusedPolicyGrad:
         self.actor, self.critic, self.kind, self.device = actor, critic, kind, critic.device
         self.obs_dim, self.hidden1, self.hidden2 = layers[0].in_features, layers[0].out_features, layers[1].out_features
         self._lib = critic._lib
-        self._params = params
+        self._slots = ParamSlots(params, 8, "FusedPolicyGrad", "actor")
         self._towers = critic.critic.towers
         self._mask = 3 if kind == _actor_lib.SAC else 1
         dev = self.device
-        # persistent .grad buffers, assigned to a parameter whose .grad is missing or unusable (no allocation per call)
-        self._gbuf = [torch.zeros_like(p, memory_format=torch.contiguous_format) for p in params]
         self._scalars = torch.zeros(2, dtype=torch.float32, device=dev)      # loss, mean log_pi
-        self._ws = torch.empty(0, dtype=torch.uint8, device=dev)
+        self._ws = Workspace(dev)
         self._cap = 0                                                        # rows the output buffers hold
         self._action = self._logpi = self._q = self._j = None
         self._acted = 0                                                      # rows of the forward the workspace holds
         self._keep = None
-        self._pptrs = (ctypes.c_void_p * 8)()
-        self._gptrs = (ctypes.c_void_p * 8)()
         # the sizes are checked now (a hidden size no kernel is compiled for raises here, not at the first call)
         self.workspace_bytes(1)
 
     @property
     def learner(self):
-        return _KIND_NAMES[self.kind].lower()
+        return KIND_NAMES[self.kind].lower()
 
     @property
     def log_pi_mean(self):
@@ -103,16 +88,14 @@ class FusedPolicyGrad:
     def workspace_bytes(self, rows):
         n = ctypes.c_int64()
         rc = self._lib.uavx_policy_grad_workspace_bytes(self.kind, self.hidden1, self.hidden2, int(rows), ctypes.byref(n))
-        _actor_lib.check(rc, f"uavx_policy_grad_workspace_bytes({_KIND_NAMES[self.kind]}, {self.hidden1}, {self.hidden2}, "
+        _actor_lib.check(rc, f"uavx_policy_grad_workspace_bytes({KIND_NAMES[self.kind]}, {self.hidden1}, {self.hidden2}, "
                              f"{rows})")
         return n.value
 
     def reserve(self, rows):
         """Grows the workspace and the output buffers to what `rows` rows need (a graph capture cannot allocate them)."""
         rows = int(rows)
-        need = self.workspace_bytes(rows)
-        if self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        if self._ws.reserve(self.workspace_bytes(rows)):
             self._acted = 0
         if self._cap < rows:
             dev, T = self.device, self._towers
@@ -124,57 +107,25 @@ class FusedPolicyGrad:
         return self
 
     def _ready(self, rows):
-        if self._cap < rows or self._ws.numel() < self.workspace_bytes(rows):
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"uavx: the workspace for {rows} rows must exist before a graph capture: call "
-                                   f"reserve({rows}) first")
+        if self._cap < rows or self._ws.buf.numel() < self.workspace_bytes(rows):
+            capture_guard("workspace", rows)
             self.reserve(rows)
 
     def _rows(self, state):
-        rows, s_stride = _rows2(state, self.obs_dim, self.device, "state")
+        rows, s_stride = rows2(state, self.obs_dim, self.device, "state")
         if rows < 1 or rows > _actor_lib.POLICY_GRAD_MAX_ROWS:
             raise ValueError(f"uavx: FusedPolicyGrad takes 1..{_actor_lib.POLICY_GRAD_MAX_ROWS} rows, got {rows}")
-        for i, p in enumerate(self._params):
-            if p.dtype != torch.float32 or p.device != self.device or not p.is_contiguous():
-                raise TypeError("uavx: FusedPolicyGrad reads contiguous float32 parameters on the actor's device")
-            self._pptrs[i] = p.data_ptr()
+        self._slots.fill_params(self.device)
         return rows, s_stride
-
-    def _grads(self):
-        out = []
-        for p, buf in zip(self._params, self._gbuf):
-            g = p.grad
-            if (g is None or g.dtype != torch.float32 or g.device != p.device or g.shape != p.shape
-                    or not g.is_contiguous()):
-                p.grad = g = buf
-            out.append(g)
-        return out
 
     def _alpha(self, alpha):
         """(value, device pointer or None) for the ABI; SAC only."""
         if self.kind != _actor_lib.SAC:
             return 0.0, None
-        if alpha is None:
-            raise ValueError("uavx: a SAC actor loss needs alpha (a float or a 1-element float32 device tensor)")
-        if torch.is_tensor(alpha):
-            _check_f32(alpha, self.device, "alpha")
-            if alpha.numel() != 1:
-                raise ValueError(f"uavx: alpha must have one element, got {tuple(alpha.shape)}")
+        if alpha_arg(alpha, self.device, "actor loss"):
             self._keep_alpha = alpha
             return 0.0, alpha.data_ptr()
         return float(alpha), None
-
-    def _noise(self, rows, noise, generator):
-        if self.kind != _actor_lib.SAC:
-            return None
-        if noise is None:
-            return torch.randn((rows, 2), generator=generator, device=self.device, dtype=torch.float32)
-        _check_f32(noise, self.device, "noise")
-        if tuple(noise.shape) != (rows, 2):
-            raise ValueError(f"uavx: noise must be [{rows}, 2], got {tuple(noise.shape)}")
-        if not noise.is_contiguous():
-            raise ValueError(f"uavx: noise must be a contiguous [{rows}, 2] tensor")
-        return noise
 
     @torch.no_grad()
     def act(self, state, noise=None, generator=None):
@@ -183,13 +134,12 @@ class FusedPolicyGrad:
         torch.randn((B, 2), generator=generator).  The activations stay in the workspace for backward_from."""
         rows, s_stride = self._rows(state)
         self._ready(rows)
-        noise = self._noise(rows, noise, generator)
-        self._keep = noise
         sac = self.kind == _actor_lib.SAC
+        self._keep = noise = noise_arg(noise, rows, self.device, generator) if sac else None
         rc = self._lib.uavx_policy_grad_forward(
-            self.kind, self.hidden1, self.hidden2, self._pptrs, state.data_ptr(), rows, s_stride,
+            self.kind, self.hidden1, self.hidden2, self._slots.pptrs, state.data_ptr(), rows, s_stride,
             noise.data_ptr() if sac else None, self._action.data_ptr(), self._logpi.data_ptr() if sac else None,
-            self._ws.data_ptr(), self._ws.numel(), _stream(self.device))
+            self._ws.buf.data_ptr(), self._ws.buf.numel(), stream(self.device))
         _actor_lib.check(rc, "uavx_policy_grad_forward")
         self._acted = rows
         return self._action[:rows * 2].view(rows, 2), (self._logpi[:rows].view(rows, 1) if sac else None)
@@ -201,21 +151,17 @@ class FusedPolicyGrad:
         the first) and returns the loss as a 0-d device tensor; SAC returns (loss, log_pi [B, 1])."""
         rows, s_stride = self._rows(state)
         T, dev = self._towers, self.device
-        for t, shape, what in ((q, (T, rows), "q"), (dqda, (T, rows, 2), "dqda")):
-            _check_f32(t, dev, what)
-            if tuple(t.shape) != shape or not t.is_contiguous():
-                raise ValueError(f"uavx: {what} must be a contiguous {list(shape)} tensor, got {tuple(t.shape)}")
+        check_buffers(((q, (T, rows), "q"), (dqda, (T, rows, 2), "dqda")), dev)
         if self._acted != rows:
             raise RuntimeError(f"uavx: backward_from({rows} rows) needs act() on the same {rows} rows first (the workspace "
                                f"holds the activations of {self._acted})")
         a_val, a_ptr = self._alpha(alpha)
-        for i, g in enumerate(self._grads()):
-            self._gptrs[i] = g.data_ptr()
+        gptrs = self._slots.fill_grads()
         sac = self.kind == _actor_lib.SAC
         rc = self._lib.uavx_policy_grad_backward(
-            self.kind, self.hidden1, self.hidden2, self._pptrs, state.data_ptr(), rows, s_stride, q.data_ptr(),
-            dqda.data_ptr(), rows, a_val, a_ptr, self._gptrs, self._scalars.data_ptr(),
-            self._scalars[1:].data_ptr() if sac else None, self._ws.data_ptr(), self._ws.numel(), _stream(dev))
+            self.kind, self.hidden1, self.hidden2, self._slots.pptrs, state.data_ptr(), rows, s_stride, q.data_ptr(),
+            dqda.data_ptr(), rows, a_val, a_ptr, gptrs, self._scalars.data_ptr(),
+            self._scalars[1:].data_ptr() if sac else None, self._ws.buf.data_ptr(), self._ws.buf.numel(), stream(dev))
         _actor_lib.check(rc, "uavx_policy_grad_backward")
         if sac:
             return self._scalars[0], self._logpi[:rows].view(rows, 1)

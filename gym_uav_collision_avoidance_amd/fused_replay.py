@@ -19,13 +19,10 @@ import ctypes
 import torch
 
 from . import _actor_lib, _lib
+from ._fused_common import Workspace, stream
 from .replay import DeviceReplay
 
 _MAX_ROWS = _actor_lib.REPLAY_MAX_ROWS
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 class FusedReplaySampler:
@@ -40,7 +37,7 @@ class FusedReplaySampler:
         self._lib = _actor_lib.load()
         self._ring = _actor_lib.ReplayRing()
         self.count = torch.zeros(1, dtype=torch.int64, device=self.device)    # what device_count=True samples from
-        self._ws = torch.empty(0, dtype=torch.uint8, device=self.device)
+        self._ws = Workspace(self.device)
         self._u = {}      # rows -> [2, 3, rows] uniforms of sample(), allocated once per batch size
 
     def workspace_bytes(self, rows):
@@ -51,9 +48,7 @@ class FusedReplaySampler:
 
     def reserve(self, rows):
         """Grows the workspace to what `rows` rows need (a graph capture cannot allocate it)."""
-        need = self.workspace_bytes(rows)
-        if self._ws.numel() < need:
-            self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+        self._ws.reserve(self.workspace_bytes(rows))
         return self
 
     def push_count(self):
@@ -121,12 +116,7 @@ class FusedReplaySampler:
         if out is not None:
             out = tuple(out)
             with_flags = with_flags or len(out) == 7
-        need = self.workspace_bytes(rows)
-        if self._ws.numel() < need:
-            if torch.cuda.is_current_stream_capturing():
-                raise RuntimeError(f"uavx: the workspace for {rows} rows must exist before a graph capture: call "
-                                   f"reserve({rows}) first")
-            self.reserve(rows)
+        self._ws.ensure(self.workspace_bytes(rows), rows)
         return with_flags, self._outputs(rows, with_flags, out)
 
     def _launch(self, u, rows, with_flags, outs, device_count):
@@ -138,8 +128,8 @@ class FusedReplaySampler:
             rc = self._lib.uavx_replay_sample(ctypes.byref(self._ring), int(self.mem.count),
                                               self.count.data_ptr() if device_count else None, u.data_ptr(), rows,
                                               outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(),
-                                              outs[4].data_ptr(), tr, en, self._ws.data_ptr() if need else None,
-                                              self._ws.numel(), _stream(self.device))
+                                              outs[4].data_ptr(), tr, en, self._ws.buf.data_ptr() if need else None,
+                                              self._ws.buf.numel(), stream(self.device))
         _actor_lib.check(rc, "uavx_replay_sample")
         return outs
 

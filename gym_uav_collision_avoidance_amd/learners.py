@@ -28,6 +28,7 @@ import os
 import torch
 
 from . import _actor_lib, policy
+from ._fused_common import capture_guard, check_f32, column, rows2, stream
 from .fused_actor import FusedActor
 from .fused_critic import FusedCritic, FusedCriticLoss, FusedTarget
 from .fused_optim import FusedAdam, soft_update
@@ -37,16 +38,6 @@ from .replay import DeviceReplay
 
 LOG_COLUMNS = _actor_lib.LEARNER_LOG_COLUMNS
 COLUMNS = ("critic_loss_1", "critic_loss_2", "actor_loss", "alpha_loss", "alpha", "actor_updated")
-
-
-def _stream(device):
-    return torch.cuda.current_stream(device).cuda_stream
-
-
-def _check_f32(t, device, what):
-    if not torch.is_tensor(t) or t.dtype != torch.float32 or t.device != device:
-        raise TypeError(f"uavx: {what} must be a float32 tensor on {device}, got {getattr(t, 'dtype', type(t))} on "
-                        f"{getattr(t, 'device', 'host')}")
 
 
 def _cpu(x):
@@ -151,24 +142,20 @@ class _FusedLearner:
         with torch.cuda.device(self.device):
             rc = self._lib.uavx_learner_tail(self.kind, li, *args, None if alpha is None else alpha.data_ptr(),
                                              self._log.data_ptr(), self.log_capacity, self._updates.data_ptr(),
-                                             int(actor_loss is not None), _stream(self.device))
+                                             int(actor_loss is not None), stream(self.device))
         _actor_lib.check(rc, "uavx_learner_tail")
 
     # ---- batches ------------------------------------------------------------------------------------------------------
     def _check_batch(self, s, a, r, s2, mask, noise):
         dev = self.device
         for t, cols, what in ((s, 10, "state"), (a, 2, "action"), (s2, 10, "next_state")):
-            _check_f32(t, dev, what)
-            if t.dim() != 2 or t.shape[1] != cols:
-                raise ValueError(f"uavx: {what} must be [B, {cols}], got {tuple(t.shape)}")
+            rows2(t, cols, dev, what, unit_stride=False)
         rows = s.shape[0]
         if rows < 1 or a.shape[0] != rows or s2.shape[0] != rows:
             raise ValueError(f"uavx: state, action and next_state must have the same B >= 1 rows, got {rows}, "
                              f"{a.shape[0]}, {s2.shape[0]}")
         for t, what in ((r, "reward"), (mask, "mask")):
-            _check_f32(t, dev, what)
-            if tuple(t.shape) not in ((rows,), (rows, 1)):
-                raise ValueError(f"uavx: {what} must be [{rows}] or [{rows}, 1], got {tuple(t.shape)}")
+            column(t, rows, dev, what)
         if self._noises == 0:
             if noise is not None:
                 raise ValueError(f"uavx: {type(self).__name__} draws no noise in its update")
@@ -180,7 +167,7 @@ class _FusedLearner:
             raise ValueError(f"uavx: {type(self).__name__}.update_batch takes {self._noises} noise tensor(s) "
                              f"([B, 2] standard normal), got {len(noise)}")
         for n in noise:
-            _check_f32(n, dev, "noise")
+            check_f32(n, dev, "noise")
             if tuple(n.shape) != (rows, 2) or not n.is_contiguous():
                 raise ValueError(f"uavx: noise must be a contiguous [{rows}, 2] tensor, got {tuple(n.shape)}")
         return rows, noise
@@ -189,9 +176,7 @@ class _FusedLearner:
         """y [rows, 1]: the reserved buffer, or a new one outside a capture."""
         if self._y is not None and self._y.shape[0] >= rows:
             return self._y[:rows]
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError(f"uavx: the buffers for {rows} rows must exist before a graph capture: call reserve({rows}) "
-                               f"first")
+        capture_guard("buffers", rows)
         return torch.empty((rows, 1), dtype=torch.float32, device=self.device)
 
     def reserve(self, rows):

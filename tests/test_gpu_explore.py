@@ -12,6 +12,7 @@ import torch
 import explore_ref as er
 from fused_ref import heads as _heads
 from gym_uav_collision_avoidance_amd import _actor_lib, policy
+from gym_uav_collision_avoidance_amd._fused_common import stream
 
 pytestmark = pytest.mark.gpu
 
@@ -187,7 +188,7 @@ def test_random_probability_by_value_and_from_the_device_slot(name):
         ex.steps.fill_(11)
         ex.ou_state.copy_(torch.from_numpy(x0).to(DEV))
         out = torch.empty((rows, 2), dtype=torch.float32, device=DEV)
-        rc = launch(ex._lib, ex.actor._stream(), kind=ex.kind, rows=rows, seed=ex.seed, raw=ex._raw.data_ptr(),
+        rc = launch(ex._lib, stream(ex.device), kind=ex.kind, rows=rows, seed=ex.seed, raw=ex._raw.data_ptr(),
                     raw_stride=ex._cols, out=out.data_ptr(), out_stride=2, state=ex.state.data_ptr(), random_prob=p,
                     noise_std=ex.noise_std, ou_sigma=ex.ou_sigma, ou_theta=ex.ou_theta, ou_dt=ex.ou_dt)
         assert rc == _actor_lib.OK
@@ -247,7 +248,7 @@ def test_reset_flags_restart_only_the_flagged_envs(packed, rows, per_env):
         flags = torch.from_numpy(byte).to(DEV)
         out = torch.empty((rows, 2), dtype=torch.float32, device=DEV)
         ex.actor._launch(obs, None, 0.0, _actor_lib.RAW, ex._raw, 2)
-        rc = launch(ex._lib, ex.actor._stream(), kind=ex.kind, rows=rows, seed=ex.seed, raw=ex._raw.data_ptr(), raw_stride=2,
+        rc = launch(ex._lib, stream(ex.device), kind=ex.kind, rows=rows, seed=ex.seed, raw=ex._raw.data_ptr(), raw_stride=2,
                     out=out.data_ptr(), out_stride=2, state=ex.state.data_ptr(), normals_out=used.data_ptr(),
                     reset_flags=flags.data_ptr(), reset_stride=N, reset_mask=2, rows_per_env=per_env,
                     ou_sigma=ex.ou_sigma, ou_theta=ex.ou_theta, ou_dt=ex.ou_dt, ou_x_initial=x_init)
@@ -285,7 +286,7 @@ def test_strided_output_touches_only_its_cells_and_rejected_calls_nothing(name):
                       out_stride=6, state=ex.state.data_ptr())
         for wrong in (dict(out_stride=3), dict(rows=0), dict(random_prob=2.0), dict(out=arena.data_ptr() + 4),
                       dict(state=ex.state.data_ptr() + 8), dict(kind=5), dict(row_offset=-1)):
-            assert launch(ex._lib, ex.actor._stream(), **dict(common, **wrong)) == _actor_lib.ERR_INVALID_ARG, wrong
+            assert launch(ex._lib, stream(ex.device), **dict(common, **wrong)) == _actor_lib.ERR_INVALID_ARG, wrong
         torch.cuda.synchronize()
         assert _same(torch.nan_to_num(arena, nan=5.0), torch.nan_to_num(before, nan=5.0)) and _same(ex.state, state)
 

@@ -10,16 +10,27 @@ update.  One JSON line per (learner, rows), carrying the library's actor_sha.
     python tools/learner_bench.py [--rows 256 4096] [--iters 30] [--out profiles/r15_learner_bench.jsonl]
     rocprofv3 --kernel-trace --stats -d out -- python tools/learner_bench.py --rows 256 --only-new 50
         # the launches' own times: only the learners' graphs run, 50 updates each
+    python tools/learner_bench.py --rows 256 --eager-host 300 --against PARENT_CHECKOUT [--turns 3] [--out FILE]
+        # host wall time per ENQUEUED eager update_batch (explicit batch, synchronised only around the timed block): what
+        # the Python bindings cost.  This tree and another checkout (built) take turns, one fresh process per turn; one
+        # JSON line per learner with both side by side.  Without --against: this tree alone, one turn in this process.
 """
 import argparse
 import json
 import os
+import statistics
+import subprocess
 import sys
+import time
 
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+_early = argparse.ArgumentParser(add_help=False)
+_early.add_argument("--package-root", default=ROOT)
+PACKAGE_ROOT = os.path.abspath(_early.parse_known_args()[0].package_root)
+sys.path.insert(0, PACKAGE_ROOT)
+import gym_uav_collision_avoidance_amd   # noqa: E402,F401 -- imported before the tools below put ROOT first
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from action_grad_bench import alternated                                          # noqa: E402
 from critic_bench import PAIRS                                                    # noqa: E402
@@ -118,8 +129,68 @@ class New:
         self.agent.run(1)
 
 
+def eager_host(kind, rows, n, dev):
+    """Host microseconds per enqueued update_batch of a learner on an explicit batch (and with the queue drained)."""
+    torch.manual_seed(0)
+    agent = CLASSES[kind](device=dev, generator=torch.Generator(device=dev).manual_seed(1))
+    g = torch.Generator(device=dev).manual_seed(2)
+    batch = (torch.randn((rows, 10), generator=g, device=dev), torch.rand((rows, 2), generator=g, device=dev) * 2 - 1,
+             torch.randn((rows,), generator=g, device=dev), torch.randn((rows, 10), generator=g, device=dev),
+             torch.ones((rows, 1), device=dev))
+    agent.reserve(rows)
+    for _ in range(50):
+        agent.update_batch(*batch)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(n):
+        agent.update_batch(*batch)
+    t1 = time.perf_counter()          # host time to ENQUEUE n updates
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    finite = bool(torch.isfinite(torch.from_numpy(agent.losses(last=1))).all())
+    agent.close()
+    return dict(host_us_per_update=(t1 - t0) / n * 1e6, us_per_update_incl_drain=(t2 - t0) / n * 1e6, finite=finite)
+
+
+def eager_host_turn(a, dev):
+    """One turn in this process: {learner: {rows: figures}} of the package this process imported."""
+    return {kind: {str(rows): eager_host(kind, rows, a.eager_host, dev) for rows in a.rows} for kind in a.learners}
+
+
+def eager_host_ab(a):
+    """The other checkout and this tree alternating, a fresh process per turn; one JSON line per (learner, rows)."""
+    arms = (("parent", os.path.abspath(a.against)), ("tree", ROOT))
+    turns = {name: [] for name, _ in arms}
+    for _ in range(a.turns):
+        for name, root in arms:
+            cmd = [sys.executable, os.path.abspath(__file__), "--package-root", root, "--eager-host", str(a.eager_host),
+                   "--rows", *map(str, a.rows), "--learners", *a.learners]
+            out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=600).stdout
+            turns[name].append(json.loads(out.strip().splitlines()[-1]))
+    lines = []
+    for kind in a.learners:
+        for rows in a.rows:
+            res = dict(learner=kind, rows=rows, updates_per_turn=a.eager_host, turns=a.turns)
+            for name, _ in arms:
+                ts = turns[name]
+                us = [t["figures"][kind][str(rows)]["host_us_per_update"] for t in ts]
+                res[name + "_actor_sha"], res[name + "_host_us_per_update"] = ts[0]["actor_sha"], us
+                res[name + "_median_us"] = statistics.median(us)
+                res[name + "_finite"] = all(t["figures"][kind][str(rows)]["finite"] for t in ts)
+            res["tree_median_within_or_below_parent_range"] = res["tree_median_us"] <= max(res["parent_host_us_per_update"])
+            lines.append(json.dumps(res))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--package-root", default=ROOT, help="import the package from this checkout instead of the tool's own")
+    ap.add_argument("--eager-host", type=int, default=0, metavar="N",
+                    help="time the host cost of N eager update_batch calls per learner instead of the graphs")
+    ap.add_argument("--against", default=None, metavar="DIR",
+                    help="with --eager-host: a built checkout of another commit that takes turns with this tree")
+    ap.add_argument("--turns", type=int, default=3)
+    ap.add_argument("--label", default=None, help="written into every graph-timing line as its `build` key")
     ap.add_argument("--rows", type=int, nargs="+", default=[256, 4096])
     ap.add_argument("--iters", type=int, default=30)
     ap.add_argument("--learners", nargs="+", default=list(CLASSES))
@@ -127,8 +198,19 @@ def main():
     ap.add_argument("--only-new", type=int, default=0, metavar="N",
                     help="run only the learners' captured updates, N each (for a kernel trace)")
     a = ap.parse_args()
+    if a.eager_host and a.against:          # the driver opens no GPU itself: one process at a time holds it
+        for line in eager_host_ab(a):
+            print(line, flush=True)
+            if a.out:
+                os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+                with open(a.out, "a") as f:
+                    f.write(line + "\n")
+        return
     dev = torch.device("cuda", 0)
     sha = _actor_lib.source_hash()
+    if a.eager_host:
+        print(json.dumps(dict(package=PACKAGE_ROOT, actor_sha=sha, figures=eager_host_turn(a, dev))), flush=True)
+        return
     env, mem = memory(dev)
     for rows in a.rows:
         for kind in a.learners:
@@ -140,6 +222,8 @@ def main():
                 continue
             base = HandComposed(kind, mem, rows, dev)
             res = dict(learner=kind, rows=rows, actor_sha=sha, iters=a.iters)
+            if a.label:
+                res = dict(build=a.label, **res)
             for k, v in alternated(dict(update_new_graph_us=new, update_hand_composed_graph_us=base), a.iters).items():
                 res[k], res[k + "_min_max"] = v[0], v[1:]
             res["new_minus_hand_composed_us"] = res["update_new_graph_us"] - res["update_hand_composed_graph_us"]
