@@ -2,6 +2,7 @@
 pytorch_ddpg_temp/ddpg.py) with every step of update_parameters as HIP launches of libuavx_actor.so:
 
     sample   FusedReplaySampler on a DeviceReplay                          (§16)
+             (NStepReplaySampler with n_step > 1 or recency > 0: n-step returns, recency-weighted draws, §22)
     target   FusedTarget: next action, target critic, y                    (§13)
     critic   FusedCriticLoss into .grad, FusedAdam step                    (§14, §15)
     actor    FusedPolicyGrad into .grad, FusedAdam step, soft updates      (§17, §18, §15)
@@ -34,6 +35,7 @@ from .fused_critic import FusedCritic, FusedCriticLoss, FusedTarget
 from .fused_optim import FusedAdam, soft_update
 from .fused_policy_grad import FusedPolicyGrad
 from .fused_replay import FusedReplaySampler
+from .fused_replay_nstep import NStepReplaySampler, check_n_step
 from .replay import DeviceReplay
 
 LOG_COLUMNS = _actor_lib.LEARNER_LOG_COLUMNS
@@ -81,7 +83,8 @@ class _FusedLearner:
     kind = None
     _noises = 0          # [B, 2] standard-normal tensors one update consumes
 
-    def _setup(self, device, generator, log_capacity, memory):
+    def _setup(self, device, generator, log_capacity, memory, n_step=1, recency=0.0):
+        self.n_step, self.recency = check_n_step(n_step, recency, type(self).__name__)
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"uavx: the learners need a GPU (cuda:N), got {self.device}: there is no CPU path")
@@ -202,12 +205,20 @@ class _FusedLearner:
         self._update(s, a, r, s2, mask, noise, self._full(u))
         self.updates += 1
 
+    def _discount(self):
+        return self.gamma
+
     def attach(self, memory):
-        """The DeviceReplay that update_parameters(None, ...) and capture() sample from."""
+        """The DeviceReplay that update_parameters(None, ...) and capture() sample from: through a FusedReplaySampler, or,
+        for a learner built with n_step > 1 or recency > 0, through an NStepReplaySampler with the learner's discount."""
         if not isinstance(memory, DeviceReplay):
             raise TypeError(f"uavx: the learners sample from a DeviceReplay, not {type(memory).__name__}")
         if self.memory is not memory:
-            self.memory, self._sampler = memory, FusedReplaySampler(memory)
+            if self.n_step == 1 and self.recency == 0.0:
+                sampler = FusedReplaySampler(memory)
+            else:           # the walk discounts with the learner's own discount, so that y = R + discount^len * mask' * (...)
+                sampler = NStepReplaySampler(memory, n_step=self.n_step, gamma=self._discount(), recency=self.recency)
+            self.memory, self._sampler = memory, sampler
             self._graphs = None
         return self
 
@@ -345,13 +356,13 @@ class FusedSAC(_FusedLearner):
 
     def __init__(self, n_states=10, n_actions=2, lr=3e-4, tau=5e-3, gamma=0.99, alpah=2, target_update_interval=1,
                  automatic_entropy_tuning=True, target_entropy=None, device="cuda", generator=None, log_capacity=1024,
-                 memory=None, hidden=256):
+                 memory=None, hidden=256, n_step=1, recency=0.0):
         self.lr, self.tau, self.gamma = lr, tau, gamma
         self.target_update_interval = int(target_update_interval)
         if self.target_update_interval < 1:
             raise ValueError(f"uavx: target_update_interval must be >= 1, got {target_update_interval}")
         self.automatic_entropy_tuning = bool(automatic_entropy_tuning)
-        self._setup(device, generator, log_capacity, memory)
+        self._setup(device, generator, log_capacity, memory, n_step, recency)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden=hidden)
         self.critic = policy.TwinQ(n_states, n_actions, hidden).to(dev)
@@ -525,13 +536,14 @@ class FusedTD3(_ActorCriticLearner):
     _noises = 1
 
     def __init__(self, state_dim=10, action_dim=2, discount=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
-                 policy_freq=2, device="cuda", generator=None, log_capacity=1024, memory=None, hidden=256):
+                 policy_freq=2, device="cuda", generator=None, log_capacity=1024, memory=None, hidden=256, n_step=1,
+                 recency=0.0):
         self.discount, self.tau, self.policy_noise, self.noise_clip = discount, tau, policy_noise, noise_clip
         self.policy_freq = int(policy_freq)
         if self.policy_freq < 1:
             raise ValueError(f"uavx: policy_freq must be >= 1, got {policy_freq}")
         self.max_action = 1
-        self._setup(device, generator, log_capacity, memory)
+        self._setup(device, generator, log_capacity, memory, n_step, recency)
         dev = self.device
         self._dims = dict(state_dim=state_dim, action_dim=action_dim, hidden=hidden)
         self.actor = policy.TD3Actor(state_dim, action_dim, hidden).to(dev)
@@ -544,6 +556,9 @@ class FusedTD3(_ActorCriticLearner):
         self.critic_optimizer = torch.optim.Adam(self.critic.parameters(), lr=3e-4)
         self._gamma = discount
         self._build(policy_noise=policy_noise, noise_clip=noise_clip)
+
+    def _discount(self):
+        return self.discount
 
     def _variants(self):
         return (True,) if self.policy_freq == 1 else (True, False)
@@ -598,10 +613,11 @@ class FusedDDPG(_ActorCriticLearner):
     _noises = 0
 
     def __init__(self, n_states=10, n_actions=2, noise_std_dev=0.2, actor_lr=1e-4, critic_lr=1e-3, tau=5e-3, gamma=0.99,
-                 device="cuda", generator=None, log_capacity=1024, memory=None, hidden1=400, hidden2=300):
+                 device="cuda", generator=None, log_capacity=1024, memory=None, hidden1=400, hidden2=300, n_step=1,
+                 recency=0.0):
         self.n_states, self.n_actions = n_states, n_actions
         self.noise_std_dev, self.tau, self.gamma = float(noise_std_dev), tau, gamma
-        self._setup(device, generator, log_capacity, memory)
+        self._setup(device, generator, log_capacity, memory, n_step, recency)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden1=hidden1, hidden2=hidden2)
         self.actor = ddpg_init(policy.DDPGActor(n_states, n_actions, hidden1, hidden2), 5e-4).to(dev)     # model.py:8,19-22
