@@ -1,5 +1,5 @@
 """ctypes binding of libuavx_actor.so: the fused actor, critic, TD-target, gradient, optimiser, replay, learner-tail and
-exploration kernels.  UNITS describes its nine units once -- header, bound ABI version, every exported function with its
+exploration kernels.  UNITS describes its ten units once -- header, bound ABI version, every exported function with its
 restype and argtypes -- and load(), _sources() and the *_HEADER, *_SYMBOLS and *_ABI_VERSION names all come from that table.
 Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so that the environment
 library and the source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device
@@ -32,6 +32,9 @@ POLICY_GRAD_MAX_ROWS = 262144   # UAVX_POLICY_GRAD_MAX_ROWS
 LEARNER_LOG_COLUMNS = 8         # UAVX_LEARNER_LOG_COLUMNS
 EXPLORE_MAX_ROWS = 16777216     # UAVX_EXPLORE_MAX_ROWS
 EXPLORE_STATE_BYTES = 16        # UAVX_EXPLORE_STATE_BYTES
+NSTEP_MAX = 8                   # UAVX_NSTEP_MAX
+NSTEP_MAX_ROWS = 1048576        # UAVX_NSTEP_MAX_ROWS
+NSTEP_SINGLE_ROWS = 1024        # UAVX_NSTEP_SINGLE_ROWS: up to here one launch and no workspace
 
 _lib_handle = None
 
@@ -40,6 +43,16 @@ class ReplayRing(ctypes.Structure):
     """uavx_replay_ring of include/uavx_replay.h."""
     _fields_ = ([(n, ctypes.c_void_p) for n in ("obs", "act", "rew", "done", "skip", "trunc", "ended")]
                 + [(n, ctypes.c_int64) for n in ("slots", "envs", "agents", "learners")])
+
+
+class NStepArgs(ctypes.Structure):
+    """uavx_nstep_args of include/uavx_nstep.h."""
+    _fields_ = [("ring", ctypes.POINTER(ReplayRing)), ("count", ctypes.c_int64), ("count_dev", ctypes.c_void_p),
+                ("u", ctypes.c_void_p), ("u_cols", ctypes.c_int32), ("n_step", ctypes.c_int32), ("gamma", ctypes.c_double),
+                ("recency", ctypes.c_float), ("rows", ctypes.c_int64), ("state", ctypes.c_void_p),
+                ("action", ctypes.c_void_p), ("reward", ctypes.c_void_p), ("next_state", ctypes.c_void_p),
+                ("mask", ctypes.c_void_p), ("length", ctypes.c_void_p), ("truncated", ctypes.c_void_p),
+                ("ended", ctypes.c_void_p), ("workspace", ctypes.c_void_p), ("workspace_bytes", ctypes.c_int64)]
 
 
 class ExploreArgs(ctypes.Structure):
@@ -117,13 +130,17 @@ UNITS = (
     _unit("exploration", "uavx_explore.h", 1, {
         "uavx_explore_version": (_i32, []),
         "uavx_explore_act": (_i32, [ctypes.POINTER(ExploreArgs), _vp])}),
+    _unit("n-step replay", "uavx_nstep.h", 1, {
+        "uavx_nstep_version": (_i32, []),
+        "uavx_nstep_workspace_bytes": (_i32, [_i64, _pi64]),
+        "uavx_nstep_sample": (_i32, [ctypes.POINTER(NStepArgs), _vp])}),
 )
 (HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER, POLICY_GRAD_HEADER, LEARNER_HEADER,
- EXPLORE_HEADER) = (u.header for u in UNITS)
+ EXPLORE_HEADER, NSTEP_HEADER) = (u.header for u in UNITS)
 (SYMBOLS, CRITIC_SYMBOLS, GRAD_SYMBOLS, OPTIM_SYMBOLS, REPLAY_SYMBOLS, ACTION_GRAD_SYMBOLS, POLICY_GRAD_SYMBOLS,
- LEARNER_SYMBOLS, EXPLORE_SYMBOLS) = (tuple(u.functions) for u in UNITS)
+ LEARNER_SYMBOLS, EXPLORE_SYMBOLS, NSTEP_SYMBOLS) = (tuple(u.functions) for u in UNITS)
 (ABI_VERSION, CRITIC_ABI_VERSION, GRAD_ABI_VERSION, OPTIM_ABI_VERSION, REPLAY_ABI_VERSION, ACTION_GRAD_ABI_VERSION,
- POLICY_GRAD_ABI_VERSION, LEARNER_ABI_VERSION, EXPLORE_ABI_VERSION) = (u.abi for u in UNITS)
+ POLICY_GRAD_ABI_VERSION, LEARNER_ABI_VERSION, EXPLORE_ABI_VERSION, NSTEP_ABI_VERSION) = (u.abi for u in UNITS)
 
 
 def _sources():
@@ -132,7 +149,7 @@ def _sources():
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the nine headers of include/, plus
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the ten headers of include/, plus
     the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
     return _native.source_hash(CSRC, _sources())
 

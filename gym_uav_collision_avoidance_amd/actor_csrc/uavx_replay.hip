@@ -1,26 +1,46 @@
-// Replay sampler (include/uavx_replay.h): DeviceReplay.sample from the ring to the learner's batch.  DESIGN.md §16.
+// Replay sampler: a draw from the ring, uniform or recency-weighted, to one row of a one-step or an n-step batch.  One set of
+// kernels behind both C interfaces: include/uavx_nstep.h is the validation and launch path, and
+// include/uavx_replay.h (DeviceReplay.sample, §16) forwards to it with n_step = 1, gamma = 1, recency = 0 and three columns
+// of uniforms.
 //
 //   rows <= 1024   sample_small   one workgroup, one thread per row: both draws and both skip flags, the choice, then the
-//                                 in-batch fallback from the waves' validity ballots kept in LDS, then the gather.  A row
-//                                 that takes another row's draw recomputes it from u (rare, and cheaper than 12 KiB of LDS).
-//   rows  > 1024   sample_draw    blocks of 1024 rows: writes every row's chosen (slot, env, agent, valid) and the block's
-//                                 first / last valid row into the workspace.
+//                                 in-batch fallback from the waves' validity ballots kept in LDS, then the walk and gather.
+//                                 A row that takes another row's draw recomputes it from u (rare, and cheaper than 12 KiB
+//                                 of LDS).
+//   rows  > 1024   sample_draw    blocks of 1024 rows: writes every row's chosen (slot, env, agent, step in the window) and
+//                                 the block's first / last valid row into the workspace.
 //                  sample_gather  the same blocks: a row without a valid row before it in its own block takes the last
 //                                 valid row of the nearest earlier block that has one, found from a 1024-bit map of the
 //                                 block summaries built once per workgroup (only by workgroups whose first row is invalid);
-//                                 then the same for the rows after it.  No workgroup waits on another: the kernel boundary
-//                                 is the only ordering between the two phases, and every search is a bounded loop.
+//                                 then the same for the rows after it; then the walk and gather.  No workgroup waits on
+//                                 another: the kernel boundary is the only ordering between the two phases, and every
+//                                 search is a bounded loop.
 //
-// Rows move as 8-byte accesses: observation rows are 40 bytes, action rows 8.  Built with -ffp-contract=off; the index is
-// one float32 multiply truncated toward zero, as torch's `(r * n).long()`.
+// The walk.  Once (k, e, i) is chosen every address of the walk is known: step j lies in slot s + j (minus slots past the
+// wrap: one compare, no division), clamped to the last step that both n_step and the ring's head allow, so that every load
+// is inside the window whatever the flags will say.  The rew, done and flag loads of ALL steps are issued together and
+// unconditionally, with the start row's observation and action, and the stop is resolved in registers afterwards (a load
+// under a run-time condition is branched around and waited for one by one: uavx_grad_impl.hpp).  Only next_state, whose
+// slot is k + len, waits for that resolution: two round trips to memory whatever n_step is, and one when the kernel is
+// built for a single step.  The kernels are instantiated for every n_step of 1..8 and for both flag layouts: a walk costs
+// the load instructions of its own steps and no more (each is 64 scattered lines per wave, and that, not latency, is
+// what a longer walk pays for), and the layout is not tested per load.  A single step loads one row's observation, action,
+// reward and done byte and the next slot's observation, and its flags only when they are asked for; −0 + 1·(double)r and
+// (1 − d)·1 round back to r and to 1 − (float)d, so the <1, *> kernels ARE the one-step sampler.
+//
+// Rows move as 8-byte accesses: observation rows are 40 bytes, action rows 8.  Built with -ffp-contract=off: the index is
+// one float32 multiply truncated toward zero, as torch's `(r * n).long()`, the return a float64 multiply and a float64 add
+// per step.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "../../include/uavx_replay.h"
+#include "../../include/uavx_nstep.h"
 
 namespace uavx_replay_k {
 
-constexpr int WG = UAVX_REPLAY_SINGLE_ROWS, WAVES = WG / 64, OBS = 10;
-constexpr int64_t MAX_BLOCKS = UAVX_REPLAY_MAX_ROWS / WG;
+static_assert(UAVX_REPLAY_MAX_ROWS == UAVX_NSTEP_MAX_ROWS && UAVX_REPLAY_SINGLE_ROWS == UAVX_NSTEP_SINGLE_ROWS,
+              "one workspace layout and one launch shape behind both interfaces");
+constexpr int WG = UAVX_NSTEP_SINGLE_ROWS, WAVES = WG / 64, OBS = 10;
+constexpr int64_t MAX_BLOCKS = UAVX_NSTEP_MAX_ROWS / WG;
 static_assert(MAX_BLOCKS <= WG, "one thread per block summary");
 
 struct Args {
@@ -30,15 +50,18 @@ struct Args {
     int64_t count;
     const int64_t *count_dev;
     const float *u;
+    int32_t cols, n;
+    double gamma;
+    float recency;
     int32_t rows;
     float *state, *action, *reward, *next_state, *mask;
-    uint8_t *truncated, *ended_out;
+    uint8_t *length, *truncated, *ended_out;
     int2 *summary;           // per block of WG rows: first and last valid row of the batch, −1 without one
-    int4 *picks;             // per row: slot, env, agent, valid
+    int4 *picks;             // per row: slot, env, agent, and the step's place in the window (−1: not valid)
 };
 
 struct Pick {
-    int32_t s, e, i;
+    int32_t s, e, i, kk;     // kk = k − lo in [0, span)
     bool valid;
 };
 
@@ -60,6 +83,14 @@ __device__ inline void window(const Args &a, int32_t &lo_mod, int32_t &span) {
     lo_mod = (int32_t)(lo % a.L);
 }
 
+// the window's span alone: no 64-bit remainder
+__device__ inline int32_t span_of(const Args &a) {
+    int64_t c = a.count_dev ? *a.count_dev : a.count;
+    if (c < 1) c = 1;
+    const int64_t T = a.L - 1;
+    return (int32_t)(c > T ? T : c);
+}
+
 __device__ inline bool skipped(const Args &a, int32_t s, int32_t e) {
     const int64_t se = (int64_t)s * a.E + e;
     return a.skip ? a.skip[se] != 0 : (a.done[se * a.N] & 2) != 0;
@@ -68,9 +99,16 @@ __device__ inline bool skipped(const Args &a, int32_t s, int32_t e) {
 // the draw row j ends up with after the redraw (steps 1 and 2)
 __device__ inline Pick draw(const Args &a, int64_t j, int32_t lo_mod, int32_t span) {
     const int64_t R = a.rows;
-    const float u0 = a.u[j], u1 = a.u[R + j], u2 = a.u[2 * R + j];
-    const float v0 = a.u[3 * R + j], v1 = a.u[4 * R + j], v2 = a.u[5 * R + j];
-    int64_t s0 = (int64_t)lo_mod + pick(u0, span), s1 = (int64_t)lo_mod + pick(v0, span);
+    const float *u = a.u + j, *v = a.u + (int64_t)a.cols * R + j;      // first draw, redraw: planes of R floats
+    const float u0 = u[0], u1 = u[R], u2 = u[2 * R], v0 = v[0], v1 = v[R], v2 = v[2 * R];
+    int32_t k0 = pick(u0, span), k1 = pick(v0, span);
+    if (a.cols == 5) {       // uniform over the launch
+        const float u3 = u[3 * R], u4 = u[4 * R], v3 = v[3 * R], v4 = v[4 * R];
+        const int32_t b0 = pick(u3, span), b1 = pick(v3, span);
+        if (u4 < a.recency && b0 > k0) k0 = b0;
+        if (v4 < a.recency && b1 > k1) k1 = b1;
+    }
+    int64_t s0 = (int64_t)lo_mod + k0, s1 = (int64_t)lo_mod + k1;
     if (s0 >= a.L) s0 -= a.L;
     if (s1 >= a.L) s1 -= a.L;
     const int32_t e0 = pick(u1, a.E), e1 = pick(v1, a.E);
@@ -79,6 +117,7 @@ __device__ inline Pick draw(const Args &a, int64_t j, int32_t lo_mod, int32_t sp
     p.s = bad0 ? (int32_t)s1 : (int32_t)s0;
     p.e = bad0 ? e1 : e0;
     p.i = pick(bad0 ? v2 : u2, a.NL);
+    p.kk = bad0 ? k1 : k0;
     p.valid = !(bad0 && bad1);
     return p;
 }
@@ -115,29 +154,79 @@ __device__ inline int after_in_block(uint64_t mine, const uint64_t *bal, int wav
     }
 }
 
-__device__ inline void gather(const Args &a, int64_t j, int32_t s, int32_t e, int32_t i) {
-    const int32_t s1 = s + 1 == a.L ? 0 : s + 1;
-    const int64_t se = (int64_t)s * a.E + e, cell = se * a.N + i, next = ((int64_t)s1 * a.E + e) * a.N + i;
-    const float2 *__restrict__ x = (const float2 *)(a.obs + cell * OBS);
-    const float2 *__restrict__ y = (const float2 *)(a.obs + next * OBS);
+// the walk from (s, e, i), kk steps into a window of span, and the row's outputs (steps 3 and 4).  NMAX >= n_step (the launch picks NMAX == n_step).
+template <int NMAX, bool PACKED>
+__device__ inline void gather(const Args &a, int64_t j, int32_t s, int32_t e, int32_t i, int32_t kk, int32_t span) {
+    // the last step the walk can reach: n_step − 1, or the newest step of the ring if that comes first
+    const int32_t rem = span - 1 - kk;
+    const int32_t top = NMAX == 1 ? 0 : (rem < a.n - 1 ? rem : a.n - 1);
+    const int64_t se0 = (int64_t)s * a.E + e, cell0 = se0 * a.N + i;
+    const bool flags = a.truncated != nullptr;
+    float rew[NMAX];
+    uint8_t dn[NMAX], sk[NMAX], en[NMAX], tr[NMAX];      // PACKED: sk holds agent 0's done byte, en and tr are not used
+#pragma unroll
+    for (int t = 0; t < NMAX; ++t) {
+        int32_t st = s + (t < top ? t : top);            // st < 2·slots: top <= span − 1 <= slots − 2
+        if (st >= a.L) st -= a.L;
+        const int64_t se = (int64_t)st * a.E + e, cell = se * a.N + i;
+        rew[t] = a.rew[cell];
+        dn[t] = a.done[cell];
+        if (NMAX == 1) {
+            // a single step stops by itself: its flags are only outputs, loaded below when they are asked for
+            sk[t] = en[t] = tr[t] = 0;
+        } else if (PACKED) {
+            sk[t] = a.done[se * a.N];
+        } else {
+            sk[t] = a.skip[se];
+            en[t] = a.ended[se];
+            tr[t] = a.trunc[se];                         // wanted or not: a load under `flags` would be waited for by itself
+        }
+    }
+    const float2 *__restrict__ x = (const float2 *)(a.obs + cell0 * OBS);
     float2 xs[OBS / 2], ys[OBS / 2];
 #pragma unroll
-    for (int k = 0; k < OBS / 2; ++k) {
-        xs[k] = x[k];
-        ys[k] = y[k];
+    for (int k = 0; k < OBS / 2; ++k) xs[k] = x[k];
+    const float2 act = *(const float2 *)(a.act + cell0 * 2);
+    // every load above is issued before the first of them is waited for: left to itself the scheduler starts resolving
+    // step 0 after half the loads, which puts a wait for memory between the two halves.  (A single step resolves nothing,
+    // and its next_state load belongs with the others.)
+    if (NMAX > 1) __builtin_amdgcn_sched_barrier(0);
+
+    // the stop, in registers: nothing below loads, and every step is computed and then selected, so that there is no
+    // conditional block for the compiler to sink a step's loads into
+    double R = -0.0, g = 1.0;                            // −0 + x is x for every x, a reward of −0 included
+    int32_t len = 1;
+    bool run = true;
+    uint8_t d_last = 0, tr_last = 0, en_last = 0;
+#pragma unroll
+    for (int t = 0; t < NMAX; ++t) {
+        const bool ended = PACKED ? (sk[t] & 4) != 0 : en[t] != 0;
+        const bool trunc = PACKED ? (sk[t] & 8) != 0 : tr[t] != 0;
+        bool stop = t == NMAX - 1 || t >= top || (dn[t] & 1) || ended;
+        if (t + 1 < NMAX) stop = stop || (PACKED ? (sk[t + 1] & 2) != 0 : sk[t + 1] != 0);
+        const double Rt = R + g * (double)rew[t], gt = g * a.gamma;
+        R = run ? Rt : R;
+        d_last = run ? (uint8_t)(dn[t] & 1) : d_last;
+        tr_last = run ? (uint8_t)trunc : tr_last;
+        en_last = run ? (uint8_t)ended : en_last;
+        run = run && !stop;
+        g = run ? gt : g;
+        len = run ? t + 2 : len;
     }
-    const float2 act = *(const float2 *)(a.act + cell * 2);
-    const float rew = a.rew[cell];
-    const uint8_t done = a.done[cell];
-    uint8_t tr = 0, en = 0;
-    if (a.truncated) {
-        if (a.skip) {
-            tr = a.trunc[se] != 0;
-            en = a.ended[se] != 0;
+
+    int32_t s1 = s + len;                                // len <= rem + 1 <= slots − 1
+    if (s1 >= a.L) s1 -= a.L;
+    const float2 *__restrict__ y = (const float2 *)(a.obs + (((int64_t)s1 * a.E + e) * a.N + i) * OBS);
+#pragma unroll
+    for (int k = 0; k < OBS / 2; ++k) ys[k] = y[k];
+    if (NMAX == 1 && flags) {                            // behind the row's other loads, as the one-step sampler has them
+        if (PACKED) {
+            const uint8_t b = a.done[se0 * a.N];
+            tr_last = (b >> 3) & 1;
+            en_last = (b >> 2) & 1;
         } else {
-            const uint8_t b = a.done[se * a.N];
-            tr = (b >> 3) & 1;
-            en = (b >> 2) & 1;
+            tr_last = a.trunc[se0] != 0;
+            en_last = a.ended[se0] != 0;
         }
     }
     float2 *__restrict__ xo = (float2 *)(a.state + j * OBS);
@@ -148,20 +237,22 @@ __device__ inline void gather(const Args &a, int64_t j, int32_t s, int32_t e, in
         yo[k] = ys[k];
     }
     *(float2 *)(a.action + j * 2) = act;
-    a.reward[j] = rew;
-    a.mask[j] = 1.0f - (float)(done & 1);
-    if (a.truncated) {
-        a.truncated[j] = tr;
-        a.ended_out[j] = en;
+    a.reward[j] = (float)R;
+    a.mask[j] = (float)((1.0 - (double)d_last) * g);
+    if (a.length) a.length[j] = (uint8_t)len;
+    if (flags) {
+        a.truncated[j] = tr_last;
+        a.ended_out[j] = en_last;
     }
 }
 
+template <int NMAX, bool PACKED>
 __global__ __launch_bounds__(WG) void sample_small(const Args a) {
     __shared__ uint64_t bal[WAVES];
     const int j = threadIdx.x;
     int32_t lo_mod, span;
     window(a, lo_mod, span);
-    Pick p{0, 0, 0, false};
+    Pick p{0, 0, 0, 0, false};
     if (j < a.rows) p = draw(a, j, lo_mod, span);
     const uint64_t mine = publish(p.valid, bal);
     if (j >= a.rows) return;
@@ -171,7 +262,7 @@ __global__ __launch_bounds__(WG) void sample_small(const Args a) {
         if (src < 0) src = a.rows - 1;
         if (src != j) p = draw(a, src, lo_mod, span);
     }
-    gather(a, j, p.s, p.e, p.i);
+    gather<NMAX, PACKED>(a, j, p.s, p.e, p.i, p.kk, span);
 }
 
 __global__ __launch_bounds__(WG) void sample_draw(const Args a) {
@@ -179,10 +270,11 @@ __global__ __launch_bounds__(WG) void sample_draw(const Args a) {
     const int64_t base = (int64_t)blockIdx.x * WG, j = base + threadIdx.x;
     int32_t lo_mod, span;
     window(a, lo_mod, span);
-    Pick p{0, 0, 0, false};
+    Pick p{0, 0, 0, 0, false};
     if (j < a.rows) {
         p = draw(a, j, lo_mod, span);
-        a.picks[j] = make_int4(p.s, p.e, p.i, p.valid ? 1 : 0);
+        // the step's place in the window rides with the validity: kk + 1 when valid, −(kk + 1) when not
+        a.picks[j] = make_int4(p.s, p.e, p.i, p.valid ? p.kk + 1 : -(p.kk + 1));
     }
     publish(p.valid, bal);
     if (threadIdx.x != 0) return;
@@ -196,13 +288,15 @@ __global__ __launch_bounds__(WG) void sample_draw(const Args a) {
     a.summary[blockIdx.x] = make_int2(first, last);
 }
 
+template <int NMAX, bool PACKED>
 __global__ __launch_bounds__(WG) void sample_gather(const Args a) {
     __shared__ uint64_t bal[WAVES], has[WAVES];
     const int64_t base = (int64_t)blockIdx.x * WG, j = base + threadIdx.x;
     const int blocks = (a.rows + WG - 1) / WG;
+    const int32_t span = NMAX == 1 ? 1 : span_of(a);     // the walk's; the slot rotation was sample_draw's business
     int4 p = make_int4(0, 0, 0, 0);
     if (j < a.rows) p = a.picks[j];
-    const uint64_t mine = publish(p.w != 0, bal);
+    const uint64_t mine = publish(p.w > 0, bal);
     // rows in front of the block's first valid row look at the other blocks; uniform over the workgroup
     int prev_last = -1, next_first = -1;
     if (!(bal[0] & 1)) {
@@ -231,7 +325,7 @@ __global__ __launch_bounds__(WG) void sample_gather(const Args a) {
         }
     }
     if (j >= a.rows) return;
-    if (p.w == 0) {
+    if (p.w <= 0) {
         const int in_before = before_in_block(mine, bal);
         int64_t src = in_before >= 0 ? base + in_before : prev_last;
         if (src < 0) {
@@ -241,8 +335,16 @@ __global__ __launch_bounds__(WG) void sample_gather(const Args a) {
         if (src < 0) src = a.rows - 1;
         if (src != j) p = a.picks[src];
     }
-    gather(a, j, p.x, p.y, p.z);
+    gather<NMAX, PACKED>(a, j, p.x, p.y, p.z, (p.w < 0 ? -p.w : p.w) - 1, span);
 }
+
+using Kernel = void (*)(const Args);
+
+// [packed][n_step − 1]
+#define UAVX_NSTEP_ROW(K, P) {K<1, P>, K<2, P>, K<3, P>, K<4, P>, K<5, P>, K<6, P>, K<7, P>, K<8, P>}
+static const Kernel SMALL[2][UAVX_NSTEP_MAX] = {UAVX_NSTEP_ROW(sample_small, false), UAVX_NSTEP_ROW(sample_small, true)};
+static const Kernel GATHER[2][UAVX_NSTEP_MAX] = {UAVX_NSTEP_ROW(sample_gather, false), UAVX_NSTEP_ROW(sample_gather, true)};
+#undef UAVX_NSTEP_ROW
 
 static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
 
@@ -260,15 +362,19 @@ extern "C" {
 
 int uavx_replay_version(void) { return UAVX_REPLAY_VERSION; }
 
-int uavx_replay_workspace_bytes(int64_t rows, int64_t *bytes) {
-    if (!bytes || rows < 0 || rows > UAVX_REPLAY_MAX_ROWS) return UAVX_ACTOR_ERR_INVALID_ARG;
+int uavx_nstep_version(void) { return UAVX_NSTEP_VERSION; }
+
+int uavx_nstep_workspace_bytes(int64_t rows, int64_t *bytes) {
+    if (!bytes || rows < 0 || rows > UAVX_NSTEP_MAX_ROWS) return UAVX_ACTOR_ERR_INVALID_ARG;
     *bytes = workspace_bytes(rows);
     return UAVX_ACTOR_OK;
 }
 
-int uavx_replay_sample(const uavx_replay_ring *ring, int64_t count, const int64_t *count_dev, const float *u, int64_t rows,
-                       float *state, float *action, float *reward, float *next_state, float *mask, uint8_t *truncated,
-                       uint8_t *ended, void *workspace, int64_t workspace_bytes_given, void *stream) {
+int uavx_replay_workspace_bytes(int64_t rows, int64_t *bytes) { return uavx_nstep_workspace_bytes(rows, bytes); }
+
+int uavx_nstep_sample(const uavx_nstep_args *g, void *stream) {
+    if (!g) return UAVX_ACTOR_ERR_INVALID_ARG;
+    const uavx_replay_ring *ring = g->ring;
     if (!ring || !ring->obs || !ring->act || !ring->rew || !ring->done) return UAVX_ACTOR_ERR_INVALID_ARG;
     const int flags = (ring->skip != nullptr) + (ring->trunc != nullptr) + (ring->ended != nullptr);
     if (flags != 0 && flags != 3) return UAVX_ACTOR_ERR_INVALID_ARG;
@@ -276,16 +382,22 @@ int uavx_replay_sample(const uavx_replay_ring *ring, int64_t count, const int64_
         ring->agents > INT32_MAX || ring->learners < 1 || ring->learners > ring->agents)
         return UAVX_ACTOR_ERR_INVALID_ARG;
     if (!aligned(ring->obs, 8) || !aligned(ring->act, 8) || !aligned(ring->rew, 4)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (count_dev ? !aligned(count_dev, 8) : count < 1) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (rows < 0 || rows > UAVX_REPLAY_MAX_ROWS) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (g->count_dev ? !aligned(g->count_dev, 8) : g->count < 1) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (g->n_step < 1 || g->n_step > UAVX_NSTEP_MAX) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!(g->gamma > 0.0 && g->gamma <= 1.0)) return UAVX_ACTOR_ERR_INVALID_ARG;              // a NaN is refused too
+    if (!(g->recency >= 0.f && g->recency <= 1.f)) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (g->u_cols != 5 && !(g->u_cols == 3 && g->recency == 0.f)) return UAVX_ACTOR_ERR_INVALID_ARG;
+    const int64_t rows = g->rows;
+    if (rows < 0 || rows > UAVX_NSTEP_MAX_ROWS) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if ((g->truncated == nullptr) != (g->ended == nullptr)) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (rows == 0) return UAVX_ACTOR_OK;
-    if (!u || !state || !action || !reward || !next_state || !mask || (truncated == nullptr) != (ended == nullptr))
-        return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!aligned(u, 4) || !aligned(state, 8) || !aligned(action, 8) || !aligned(next_state, 8) || !aligned(reward, 4) ||
-        !aligned(mask, 4))
+    if (!g->u || !g->state || !g->action || !g->reward || !g->next_state || !g->mask) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!aligned(g->u, 4) || !aligned(g->state, 8) || !aligned(g->action, 8) || !aligned(g->next_state, 8) ||
+        !aligned(g->reward, 4) || !aligned(g->mask, 4))
         return UAVX_ACTOR_ERR_INVALID_ARG;
     const int64_t need = workspace_bytes(rows);
-    if (need > 0 && (!workspace || workspace_bytes_given < need || !aligned(workspace, 16))) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (need > 0 && (!g->workspace || g->workspace_bytes < need || !aligned(g->workspace, 16)))
+        return UAVX_ACTOR_ERR_INVALID_ARG;
 
     Args a{};
     a.obs = ring->obs;
@@ -299,29 +411,63 @@ int uavx_replay_sample(const uavx_replay_ring *ring, int64_t count, const int64_
     a.E = (int32_t)ring->envs;
     a.N = (int32_t)ring->agents;
     a.NL = (int32_t)ring->learners;
-    a.count = count;
-    a.count_dev = count_dev;
-    a.u = u;
+    a.count = g->count;
+    a.count_dev = g->count_dev;
+    a.u = g->u;
+    a.cols = g->u_cols;
+    a.n = g->n_step;
+    a.gamma = g->gamma;
+    a.recency = g->recency;
     a.rows = (int32_t)rows;
-    a.state = state;
-    a.action = action;
-    a.reward = reward;
-    a.next_state = next_state;
-    a.mask = mask;
-    a.truncated = truncated;
-    a.ended_out = ended;
+    a.state = g->state;
+    a.action = g->action;
+    a.reward = g->reward;
+    a.next_state = g->next_state;
+    a.mask = g->mask;
+    a.length = g->length;
+    a.truncated = g->truncated;
+    a.ended_out = g->ended;
+    const int packed = ring->skip == nullptr, level = a.n - 1;
     const hipStream_t st = (hipStream_t)stream;
     if (rows <= WG) {
-        hipLaunchKernelGGL(sample_small, dim3(1), dim3((unsigned)((rows + 63) / 64 * 64)), 0, st, a);
+        hipLaunchKernelGGL(SMALL[packed][level], dim3(1), dim3((unsigned)((rows + 63) / 64 * 64)), 0, st, a);
         return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
     }
-    a.summary = (int2 *)workspace;
-    a.picks = (int4 *)((char *)workspace + summary_bytes(rows));
+    a.summary = (int2 *)g->workspace;
+    a.picks = (int4 *)((char *)g->workspace + summary_bytes(rows));
     const unsigned blocks = (unsigned)((rows + WG - 1) / WG);
     hipLaunchKernelGGL(sample_draw, dim3(blocks), dim3(WG), 0, st, a);
     if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(sample_gather, dim3(blocks), dim3(WG), 0, st, a);
+    hipLaunchKernelGGL(GATHER[packed][level], dim3(blocks), dim3(WG), 0, st, a);
     return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
+}
+
+// One step, uniform draws, three columns of uniforms, no length.  With rows = 0 this entry has always answered before it
+// looked at the output flags, and uavx_nstep_sample looks at that pair first: they are not handed on then.
+int uavx_replay_sample(const uavx_replay_ring *ring, int64_t count, const int64_t *count_dev, const float *u, int64_t rows,
+                       float *state, float *action, float *reward, float *next_state, float *mask, uint8_t *truncated,
+                       uint8_t *ended, void *workspace, int64_t workspace_bytes_given, void *stream) {
+    uavx_nstep_args g{};
+    g.ring = ring;
+    g.count = count;
+    g.count_dev = count_dev;
+    g.u = u;
+    g.u_cols = 3;
+    g.n_step = 1;
+    g.gamma = 1.0;
+    g.recency = 0.f;
+    g.rows = rows;
+    g.state = state;
+    g.action = action;
+    g.reward = reward;
+    g.next_state = next_state;
+    g.mask = mask;
+    g.length = nullptr;
+    g.truncated = rows == 0 ? nullptr : truncated;
+    g.ended = rows == 0 ? nullptr : ended;
+    g.workspace = workspace;
+    g.workspace_bytes = workspace_bytes_given;
+    return uavx_nstep_sample(&g, stream);
 }
 
 }  // extern "C"

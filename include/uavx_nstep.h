@@ -1,9 +1,9 @@
-/* uavx_nstep.h — C ABI of the n-step replay sampler in libuavx_replayx.so: a draw from the zero-copy ring of replay.py
+/* uavx_nstep.h — C ABI of the n-step replay sampler in libuavx_actor.so: a draw from the zero-copy ring of replay.py
  * (uavx_replay.h describes it) turned into one row of an n-step batch on MI355X (gfx950) — the discounted return of up to
  * n_step steps, the observation that many steps on and the discount the bootstrap still carries — with the start row drawn
  * uniformly or, per row, with a weight that grows linearly with recency.  ONE kernel launch up to UAVX_NSTEP_SINGLE_ROWS
- * rows and TWO above, like uavx_replay_sample, whose draw, redraw and fallback rules it keeps.  A library of its own:
- * libuavx_actor.so, its headers and its source hash do not change with it.
+ * rows and TWO above, like uavx_replay_sample, whose draw, redraw and fallback rules it keeps: the same kernels serve
+ * both, and uavx_replay_sample is this call with n_step = 1, gamma = 1, recency = 0, u_cols = 3 and no length.
  *
  * With c = max(1, count), T = slots − 1, lo = max(0, c − T), span = c − lo as in uavx_replay.h, idx(u, n) its
  * min(trunc(u·(float)n), n − 1) with the same out-of-range rule (a product that is negative or NaN gives 0, one at or past

@@ -1,25 +1,30 @@
-"""Host-side checks of the learner bindings' shared layer: _actor_lib's table of units gives the hash, the
-sources and every public constant the hand-written module gave (values recorded at commit 1ba5a5c), covers every exported
-symbol, and every class built on the kind tables and on critic_handle refuses a wrong class, a wrong pair and a CPU module
-with the message it had there -- before the library is loaded, so without a GPU."""
+"""Host-side checks of the learner bindings' shared layer: _actor_lib's table of units gives the
+sources and every public constant the hand-written module gave (values recorded at commit 1ba5a5c; the tenth unit, the
+n-step sampler, and the per-file hashes at 9a32f7c), covers every exported symbol, and every class built on the kind
+tables and on critic_handle refuses a wrong class, a wrong pair and a CPU module with the message it had there -- before
+the library is loaded, so without a GPU."""
+import hashlib
+import json
 import os
 import re
 
 import pytest
 import torch
 
-from gym_uav_collision_avoidance_amd import _actor_lib, policy
+from gym_uav_collision_avoidance_amd import _actor_lib, _native, policy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PARENT_HASH = "ab517ee91bb05350"
+# source_hash() at the commit that moved the n-step sampler into uavx_replay.hip (ab517ee91bb05350 before it)
+MERGED_HASH = "a056e385b4f6651e"
 PARENT_SOURCES = [
     "uavx_action_grad.hip", "uavx_actor.hip", "uavx_actor_impl.hpp", "uavx_critic.hip", "uavx_critic_grad.hip",
     "uavx_explore.hip", "uavx_grad_common.hip", "uavx_grad_impl.hpp", "uavx_learner.hip", "uavx_optim.hip",
     "uavx_policy_grad.hip", "uavx_replay.hip", "uavx_actor.h", "uavx_critic.h", "uavx_critic_grad.h", "uavx_optim.h",
-    "uavx_replay.h", "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h"]
-UNIT_NAMES = ("", "CRITIC_", "GRAD_", "OPTIM_", "REPLAY_", "ACTION_GRAD_", "POLICY_GRAD_", "LEARNER_", "EXPLORE_")
+    "uavx_replay.h", "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h", "uavx_nstep.h"]
+UNIT_NAMES = ("", "CRITIC_", "GRAD_", "OPTIM_", "REPLAY_", "ACTION_GRAD_", "POLICY_GRAD_", "LEARNER_", "EXPLORE_",
+              "NSTEP_")
 PARENT_HEADERS = ("uavx_actor.h", "uavx_critic.h", "uavx_critic_grad.h", "uavx_optim.h", "uavx_replay.h",
-                  "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h")
+                  "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h", "uavx_nstep.h")
 PARENT_SYMBOLS = (
     ("uavx_actor_version", "uavx_actor_strerror", "uavx_actor_create", "uavx_actor_destroy", "uavx_actor_pack",
      "uavx_actor_forward"),
@@ -32,20 +37,33 @@ PARENT_SYMBOLS = (
     ("uavx_policy_grad_version", "uavx_policy_grad_workspace_bytes", "uavx_policy_grad_forward",
      "uavx_policy_grad_backward"),
     ("uavx_learner_version", "uavx_learner_tail"),
-    ("uavx_explore_version", "uavx_explore_act"))
+    ("uavx_explore_version", "uavx_explore_act"),
+    ("uavx_nstep_version", "uavx_nstep_workspace_bytes", "uavx_nstep_sample"))
 PARENT_CONSTANTS = dict(
     SAC=0, TD3=1, DDPG=2, F32=0, BF16=1, RAW=0, DETERMINISTIC=1, SAC_SAMPLE=2, ADD_CLAMP=3, OK=0, ERR_INVALID_ARG=-1,
     ERR_HIP=-2, ERR_UNSUPPORTED=-3, ERR_NOT_PACKED=-4, SPLIT_ROWS=16384, GRAD_MSE=0, GRAD_L1=1, GRAD_MAX_ROWS=262144,
     OPTIM_MAX_TENSORS=16, REPLAY_MAX_ROWS=1048576, REPLAY_SINGLE_ROWS=1024, ACTION_GRAD_MAX_ROWS=262144,
-    POLICY_GRAD_MAX_ROWS=262144, LEARNER_LOG_COLUMNS=8, EXPLORE_MAX_ROWS=16777216, EXPLORE_STATE_BYTES=16)
+    POLICY_GRAD_MAX_ROWS=262144, LEARNER_LOG_COLUMNS=8, EXPLORE_MAX_ROWS=16777216, EXPLORE_STATE_BYTES=16, NSTEP_MAX=8,
+    NSTEP_MAX_ROWS=1048576, NSTEP_SINGLE_ROWS=1024)
 WORDS = ("actor", "critic", "critic-gradient", "optimiser", "replay", "action-gradient", "policy-gradient", "learner",
-         "exploration")
+         "exploration", "n-step replay")
 
 
 def test_hash_and_sources_are_the_parents():
-    assert _actor_lib.source_hash() == PARENT_HASH
-    assert [os.path.basename(p) for p in _actor_lib._sources()] == PARENT_SOURCES
-    assert all(os.path.isfile(p) for p in _actor_lib._sources())
+    """Nothing outside the replay unit moved: every source but uavx_replay.hip has the code it had at 9a32f7c
+    (golden/actor_sources_parent.json, written there by golden/make_actor_sources.py), and the only file the library
+    gained is the n-step header."""
+    sources = _actor_lib._sources()
+    assert [os.path.basename(p) for p in sources] == PARENT_SOURCES
+    assert all(os.path.isfile(p) for p in sources)
+    parent = json.load(open(os.path.join(ROOT, "tests", "golden", "actor_sources_parent.json")))
+    assert set(PARENT_SOURCES) == set(parent) | {"uavx_nstep.h"} and "uavx_nstep.h" not in parent
+    for p in sources:
+        name = os.path.basename(p)
+        if name not in ("uavx_replay.hip", "uavx_nstep.h"):
+            code = _native.code_only(open(p, encoding="utf-8").read())
+            assert hashlib.sha256(code.encode()).hexdigest() == parent[name], name
+    assert _actor_lib.source_hash() == MERGED_HASH
 
 
 def test_public_constants_keep_their_parent_values():

@@ -1,4 +1,4 @@
-"""NStepReplaySampler (libuavx_replayx.so, include/uavx_nstep.h) on the MI355X: for one step bit-identical to
+"""NStepReplaySampler (libuavx_actor.so, include/uavx_nstep.h) on the MI355X: for one step bit-identical to
 FusedReplaySampler.sample and DeviceReplay.sample on rings written by a real env; for 2, 3 and 8 steps bit-identical to
 tests/nstep_ref.py on crafted rings whose every start row is enumerated (each of the five ways a walk ends, both flag
 layouts, counts below, at and past the wrap), on walks across the slot wrap and up to the ring's head, on the fallback

@@ -317,3 +317,48 @@ def test_graph_capture_follows_the_device_count():
             fresh.sample_from_uniforms(u, out=bufs, device_count=True)
     torch.cuda.synchronize()
     env.close()
+
+
+@pytest.mark.parametrize("packed", [False, True])
+def test_the_c_entry_uavx_replay_sample_equals_the_reference(packed):
+    """The Python layer launches through uavx_nstep_sample; uavx_replay_sample, which forwards to it, is called here as a
+    C caller would: ring struct, uniforms and buffers by address, one launch (65 rows) and two (1025), with and without
+    the flag outputs, and once with the device count."""
+    import ctypes
+    from gym_uav_collision_avoidance_amd import _actor_lib
+    lib = _actor_lib.load()
+    env, mem = _mem(14, learners=3, packed=packed)
+    ring = _actor_lib.ReplayRing(obs=mem.obs.data_ptr(), act=mem.act.data_ptr(), rew=mem.rew.data_ptr(),
+                                 done=mem.done.data_ptr(), slots=L, envs=E, agents=N, learners=3)
+    if not packed:
+        ring.skip, ring.trunc, ring.ended = mem.skip.data_ptr(), mem.trunc.data_ptr(), mem.ended.data_ptr()
+    count_dev = torch.full((1,), mem.count, dtype=torch.int64, device=DEV)
+    arrays = _arrays(mem)
+    fallbacks = 0
+    for rows, flags, dev_count in ((65, True, False), (65, False, False), (1025, True, False), (1025, False, False),
+                                   (1025, True, True)):
+        u_np = np.random.default_rng(rows + flags).random((2, 3, rows), dtype=np.float32)
+        want = replay_ref.sample(u_np, count=mem.count, T=T, num_learners=3, **arrays)
+        u = torch.from_numpy(u_np).to(DEV)
+        outs = [torch.full(s, -7.0, device=DEV) for s in ((rows, 10), (rows, 2), (rows,), (rows, 10), (rows,))]
+        tr, en = (torch.full((rows,), 9, dtype=torch.uint8, device=DEV) for _ in range(2))
+        need = ctypes.c_int64(-1)
+        assert lib.uavx_replay_workspace_bytes(rows, ctypes.byref(need)) == _actor_lib.OK
+        assert (need.value == 0) == (rows <= _actor_lib.REPLAY_SINGLE_ROWS)
+        ws = torch.empty(max(need.value, 16), dtype=torch.uint8, device=DEV)
+        # a wrong host count beside the device count: the kernel reads the device's
+        rc = lib.uavx_replay_sample(ctypes.byref(ring), 1 if dev_count else mem.count,
+                                    count_dev.data_ptr() if dev_count else None, u.data_ptr(), rows,
+                                    *(o.data_ptr() for o in outs), tr.data_ptr() if flags else None,
+                                    en.data_ptr() if flags else None, ws.data_ptr() if need.value else None, need.value,
+                                    torch.cuda.current_stream(DEV).cuda_stream)
+        assert rc == _actor_lib.OK
+        torch.cuda.synchronize()
+        for x, w in zip(outs, want[:5]):
+            x = x.cpu().numpy()
+            assert x.shape == w.shape and x.dtype == w.dtype and np.array_equal(x.view(np.int32), w.view(np.int32))
+        for x, w in zip((tr, en), want[5:7]):
+            assert np.array_equal(x.cpu().numpy(), w.astype(np.uint8) if flags else np.full(rows, 9, dtype=np.uint8))
+        fallbacks += int((want[7] != np.arange(rows)).sum())
+    assert fallbacks > 0                                  # reset rows were drawn twice: the fallback had work
+    env.close()

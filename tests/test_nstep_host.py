@@ -1,8 +1,8 @@
-"""Host-side checks of the n-step replay sampler (libuavx_replayx.so, include/uavx_nstep.h): the library builds for gfx950
+"""Host-side checks of the n-step replay sampler (libuavx_actor.so, include/uavx_nstep.h): the library builds for gfx950
 without a GPU and carries its source hash, exports exactly what its header declares, refuses every bad argument before
-touching a device, its kernels use no scratch and spill nothing, the pinned libuavx_actor.so is untouched by it, and the
-numpy restatement the GPU tests trust (nstep_ref.py) equals a per-row loop written from the header's prose, equals
-replay_ref.sample for one step, and draws step indices with a cumulative distribution of exactly (m/span)^2."""
+touching a device, its kernels use no scratch and spill nothing, it is one unit of ten beside the one-step interface it
+shares its kernels with, and the numpy restatement the GPU tests trust (nstep_ref.py) equals a per-row loop written from
+the header's prose, equals replay_ref.sample for one step, and draws step indices with a cumulative distribution of exactly (m/span)^2."""
 import ctypes
 import importlib.util
 import os
@@ -19,9 +19,9 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def _xlib():
-    from gym_uav_collision_avoidance_amd import _replayx_lib
-    _replayx_lib.build()
-    return _replayx_lib
+    from gym_uav_collision_avoidance_amd import _actor_lib
+    _actor_lib.build()
+    return _actor_lib
 
 
 def _kernels():
@@ -35,29 +35,30 @@ def _kernels():
 
 def test_library_cross_compiles_and_carries_its_source_hash():
     x = _xlib()
-    assert os.path.basename(x.LIB_PATH) == "libuavx_replayx.so" and os.path.isfile(x.LIB_PATH)
-    assert x.HEADER == os.path.join(ROOT, "include", "uavx_nstep.h") and x.HEADER in x._sources()
-    assert any(f.endswith(os.path.join("replay_csrc", "uavx_nstep.hip")) for f in x._sources())
-    assert f"UAVX_REPLAYX_SRC_HASH={x.source_hash()}".encode() + b"\0" in open(x.LIB_PATH, "rb").read()
+    assert os.path.basename(x.LIB_PATH) == "libuavx_actor.so" and os.path.isfile(x.LIB_PATH)
+    assert x.NSTEP_HEADER == os.path.join(ROOT, "include", "uavx_nstep.h") and x.NSTEP_HEADER in x._sources()
+    assert any(f.endswith(os.path.join("actor_csrc", "uavx_replay.hip")) for f in x._sources())
+    assert f"UAVX_ACTOR_SRC_HASH={x.source_hash()}".encode() + b"\0" in open(x.LIB_PATH, "rb").read()
     assert x._up_to_date()
     mk = open(os.path.join(x.CSRC, "Makefile")).read()
     flags = re.search(r"^HIPFLAGS \?= (.*)$", mk, re.M).group(1).split()
-    assert flags == "-O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fPIC -Wall".split()
-    assert "UAVX_REPLAYX_SRC_HASH" in mk and "OUT ?= libuavx_replayx.so" in mk and "SRCHASH ?=" in mk
+    assert flags == "-O3 -std=c++17 --offload-arch=$(ARCH) -ffp-contract=off -fPIC -Wall -Wno-unused-function".split()
+    assert "UAVX_ACTOR_SRC_HASH" in mk and "OUT ?= libuavx_actor.so" in mk and "SRCHASH ?=" in mk
+    assert "uavx_nstep.h" in mk and "uavx_replay.hip" in mk
     # the kernels are gfx950 code objects
     assert b"gfx950" in open(x.LIB_PATH, "rb").read()
 
 
 def test_library_exports_exactly_what_the_header_declares():
     x = _xlib()
-    hdr = open(x.HEADER).read()
+    hdr = open(x.NSTEP_HEADER).read()
     declared = set(re.findall(r"\b(uavx_nstep_[a-z_0-9]*)\s*\(", hdr))
-    assert declared == set(x.SYMBOLS) == {"uavx_nstep_version", "uavx_nstep_workspace_bytes", "uavx_nstep_sample"}
-    assert x.SYMBOLS[0] == x.UNIT.version == "uavx_nstep_version"
+    assert declared == set(x.NSTEP_SYMBOLS) == {"uavx_nstep_version", "uavx_nstep_workspace_bytes", "uavx_nstep_sample"}
+    assert x.NSTEP_SYMBOLS[0] == x.UNITS[-1].version == "uavx_nstep_version" and x.UNITS[-1].word == "n-step replay"
     lib = x.load()
     for name in sorted(declared):
         assert hasattr(lib, name), name
-    assert lib.uavx_nstep_version() == x.ABI_VERSION == 1 and "#define UAVX_NSTEP_VERSION 1" in hdr
+    assert lib.uavx_nstep_version() == x.NSTEP_ABI_VERSION == 1 and "#define UAVX_NSTEP_VERSION 1" in hdr
     assert f"#define UAVX_NSTEP_MAX {x.NSTEP_MAX}" in hdr and x.NSTEP_MAX == 8
     assert f"#define UAVX_NSTEP_MAX_ROWS {x.NSTEP_MAX_ROWS}" in hdr and x.NSTEP_MAX_ROWS == 2 ** 20
     assert f"#define UAVX_NSTEP_SINGLE_ROWS {x.NSTEP_SINGLE_ROWS}" in hdr and x.NSTEP_SINGLE_ROWS == 1024
@@ -66,15 +67,21 @@ def test_library_exports_exactly_what_the_header_declares():
     body = re.sub(r"/\*.*?\*/", "", body, flags=re.S)
     fields = [re.search(r"(\w+)\s*$", d).group(1) for d in body.split(";") if d.strip()]
     assert fields == [n for n, _ in x.NStepArgs._fields_]
-    from gym_uav_collision_avoidance_amd import _actor_lib
-    assert x.ReplayRing is _actor_lib.ReplayRing
+    assert x.NStepArgs._fields_[0][1] is ctypes.POINTER(x.ReplayRing)
 
 
-def test_the_pinned_actor_library_is_untouched():
-    from gym_uav_collision_avoidance_amd import _actor_lib
-    assert _actor_lib.source_hash() == "ab517ee91bb05350"
-    assert not any("nstep" in os.path.basename(f) for f in _actor_lib._sources())
-    assert len(_actor_lib.UNITS) == 9
+def test_one_library_serves_both_sampler_interfaces():
+    x = _xlib()
+    assert len(x.UNITS) == 10
+    pkg = os.path.join(ROOT, "gym_uav_collision_avoidance_amd")
+    assert not os.path.exists(os.path.join(pkg, "replay_csrc"))
+    assert importlib.util.find_spec("gym_uav_collision_avoidance_amd._replayx_lib") is None
+    assert [os.path.basename(f) for f in x._sources() if "nstep" in os.path.basename(f)] == ["uavx_nstep.h"]
+    lib = x.load()                                            # one handle, one file: both interfaces resolve in it
+    assert lib._name == x.LIB_PATH
+    for name in x.NSTEP_SYMBOLS + x.REPLAY_SYMBOLS:
+        assert hasattr(lib, name), name
+    assert lib.uavx_nstep_version() == lib.uavx_replay_version() == 1
 
 
 def test_workspace_bytes():
@@ -159,7 +166,8 @@ def test_bad_arguments_refused_before_any_device_call():
 
 def test_kernels_use_no_scratch_and_spill_nothing():
     rows = _kernels()
-    assert rows and all(r["name"].startswith("uavx_nstep_k::") for r in rows), sorted(r["name"] for r in rows)
+    rows = [r for r in rows if r["name"].startswith("uavx_replay_k::")]
+    assert rows and not any("uavx_nstep_k::" in r["name"] for r in _kernels())
     names = sorted(r["name"] for r in rows)
     # one small and one gather kernel per n_step of 1..8 and flag layout, and the draw kernel
     assert sum("sample_small<" in n for n in names) == 16 and sum("sample_gather<" in n for n in names) == 16

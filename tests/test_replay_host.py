@@ -115,13 +115,18 @@ def test_replay_bad_arguments_rejected_before_any_device_call():
     assert call(ws=P + 8) == bad                                                              # workspace not 16-byte aligned
     # rows = 0 enqueues nothing and looks at no buffer
     assert call(rows=0, u=None, s=None, ws=None, ws_bytes=0) == a.OK
+    assert call(rows=0, tr=None) == a.OK and call(rows=0, en=None) == a.OK      # nor at the pair of flag outputs
     assert call(rows=0, ring_=ring(slots=1)) == bad
 
 
 def test_replay_kernels_within_budget():
     rows = _kernels()
-    mine = [r for r in rows if r["name"].startswith("uavx_replay_k::")]
-    assert 1 <= len(mine) <= 3, sorted(r["name"] for r in mine)
+    # the one-step instantiations of the shared sampler kernels: what uavx_replay_sample launches
+    mine = [r for r in rows if r["name"].startswith("uavx_replay_k::")
+            and re.search(r"sample_(small|gather)<1, |sample_draw$", r["name"])]
+    assert sorted(r["name"].split("::")[1] for r in mine) == [
+        "sample_draw", "sample_gather<1, false>", "sample_gather<1, true>", "sample_small<1, false>",
+        "sample_small<1, true>"], sorted(r["name"] for r in rows if r["name"].startswith("uavx_replay_k::"))
     for r in mine:
         assert r["vgpr_spill_count"] == 0 and r["sgpr_spill_count"] == 0, r
         assert r["private_segment_fixed_size"] == 0, r

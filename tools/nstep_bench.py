@@ -1,12 +1,12 @@
 #!/usr/bin/env python3
-"""Times one graph-captured sample of NStepReplaySampler (libuavx_replayx.so) beside FusedReplaySampler's
+"""Times one graph-captured sample of NStepReplaySampler (libuavx_actor.so) beside FusedReplaySampler's
 (§16) on the same ring in the same process: 1024 envs x 4 agents, horizon 256, stepped past the wrap with step_cap = 1500.
 
 Per batch size, in this order: the one-step baseline twice, back to back (the larger relative difference of the two is
-the noise margin), n_step = 1 / recency = 0 (the same work: it may be slower than the baseline by that margin at the
-most, which is to say no slower than the slower of the two baseline timings), then n_step 3, 5, 8 with recency 0.8, which
-have no bound.  Every figure is the median of three time_us() runs of graph replays (critic_bench.time_us: itself the
-median of three timed loops).  One JSON line per batch size, carrying both libraries' source hashes.
+the noise margin), n_step = 1 / recency = 0 (the same kernels through the same launch path as the baseline: a third
+timing of it, reported against that margin), then n_step 3, 5, 8 with recency 0.8, which have no bound.  Every figure is
+the median of three time_us() runs of graph replays (critic_bench.time_us: itself the median of three timed loops).  One
+JSON line per batch size, carrying the library's actor_sha.
 
     python tools/nstep_bench.py [--rows 256 262144] [--iters 200]
 """
@@ -22,7 +22,7 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from critic_bench import time_us                                                        # noqa: E402
 from replay_bench import graphed                                                        # noqa: E402
-from gym_uav_collision_avoidance_amd import BatchedMultiUAVWorld2D, _actor_lib, _replayx_lib   # noqa: E402
+from gym_uav_collision_avoidance_amd import BatchedMultiUAVWorld2D, _actor_lib           # noqa: E402
 from gym_uav_collision_avoidance_amd.fused_replay import FusedReplaySampler            # noqa: E402
 from gym_uav_collision_avoidance_amd.fused_replay_nstep import NStepReplaySampler      # noqa: E402
 from gym_uav_collision_avoidance_amd.replay import DeviceReplay                         # noqa: E402
@@ -65,9 +65,8 @@ def main():
         if not all(torch.equal(x, y) for x, y in zip(one.sample(rows, generator=g1, with_flags=True),
                                                      same.sample(rows, generator=g2, with_flags=True))):
             raise SystemExit(f"nstep_bench: n_step = 1 and the one-step sampler differ at {rows} rows")
-        res = dict(rows=rows, actor_sha=_actor_lib.source_hash(), replayx_sha=_replayx_lib.source_hash(), envs=a.envs,
-                   agents=4, horizon=a.horizon, steps=mem.count, step_cap=a.step_cap, reset_row_share=skip_share,
-                   iters=a.iters)
+        res = dict(rows=rows, actor_sha=_actor_lib.source_hash(), envs=a.envs, agents=4, horizon=a.horizon,
+                   steps=mem.count, step_cap=a.step_cap, reset_row_share=skip_share, iters=a.iters)
         (base_a, _), (base_b, _) = timed(one, rows), timed(one, rows)
         res.update(baseline_us=[base_a[1], base_b[1]], baseline_min_max_us=[base_a[0], base_a[2], base_b[0], base_b[2]])
         margin = abs(base_a[1] - base_b[1]) / min(base_a[1], base_b[1])
