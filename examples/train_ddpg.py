@@ -35,13 +35,16 @@ ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--checkpoint", type=str, default=None, help="directory to write actor.chpt and critic.chpt into at the end")
 ap.add_argument("--n-step", type=int, default=1, help="steps of return summed per sampled row (1..8)")
 ap.add_argument("--recency", type=float, default=0.0, help="share of rows drawn with a weight that grows with recency")
+ap.add_argument("--prioritized", type=float, default=None, metavar="ALPHA",
+                help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
 venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=args.seed)
 mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
-agent = FusedDDPG(noise_std_dev=args.noise_std_dev, device=dev, memory=mem, n_step=args.n_step, recency=args.recency)
+agent = FusedDDPG(noise_std_dev=args.noise_std_dev, device=dev, memory=mem, n_step=args.n_step, recency=args.recency,
+                  prioritized=args.prioritized)
 explore = agent.exploration(mem, seed=args.seed, warmup_steps=args.warmup, reset_on_episode=args.reset_ou_per_episode)
 
 t0 = time.perf_counter()

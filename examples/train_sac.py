@@ -29,6 +29,8 @@ ap.add_argument("--report", type=int, default=500)
 ap.add_argument("--checkpoint", type=str, default=None, help="directory to write weights.chpt into at the end")
 ap.add_argument("--n-step", type=int, default=1, help="steps of return summed per sampled row (1..8)")
 ap.add_argument("--recency", type=float, default=0.0, help="share of rows drawn with a weight that grows with recency")
+ap.add_argument("--prioritized", type=float, default=None, metavar="ALPHA",
+                help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -36,7 +38,8 @@ venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=0)
 mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
 gen = torch.Generator(device=dev).manual_seed(0)
-agent = FusedSAC(device=dev, generator=gen, memory=mem, n_step=args.n_step, recency=args.recency)
+agent = FusedSAC(device=dev, generator=gen, memory=mem, n_step=args.n_step, recency=args.recency,
+                 prioritized=args.prioritized)
 
 t0 = time.perf_counter()
 for t in range(args.steps):

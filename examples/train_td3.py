@@ -6,6 +6,7 @@ action plus clipped Gaussian noise drawn from Philox streams keyed by the global
 
     python examples/train_td3.py [--envs 1024] [--agents 4] [--steps 2000] [--batch 256] [--warmup 64]
                                   [--n-step 1] [--recency 0]       # n-step returns, recency-weighted draws
+                                  [--prioritized 0.6]              # proportional prioritized replay
 """
 import argparse
 import os
@@ -33,6 +34,8 @@ ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--checkpoint", type=str, default=None, help="directory to write weights.chpt into at the end")
 ap.add_argument("--n-step", type=int, default=1, help="steps of return summed per sampled row (1..8)")
 ap.add_argument("--recency", type=float, default=0.0, help="share of rows drawn with a weight that grows with recency")
+ap.add_argument("--prioritized", type=float, default=None, metavar="ALPHA",
+                help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency")
 args = ap.parse_args()
 
 dev = torch.device("cuda", 0)
@@ -40,7 +43,8 @@ venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=args.see
 mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
 gen = torch.Generator(device=dev).manual_seed(args.seed)
-agent = FusedTD3(device=dev, generator=gen, memory=mem, n_step=args.n_step, recency=args.recency)
+agent = FusedTD3(device=dev, generator=gen, memory=mem, n_step=args.n_step, recency=args.recency,
+                 prioritized=args.prioritized)
 explore = agent.exploration(mem, seed=args.seed, warmup_steps=args.warmup, noise_std=args.noise_std)
 
 t0 = time.perf_counter()

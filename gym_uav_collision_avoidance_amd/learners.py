@@ -2,7 +2,8 @@
 pytorch_ddpg_temp/ddpg.py) with every step of update_parameters as HIP launches of libuavx_actor.so:
 
     sample   FusedReplaySampler on a DeviceReplay                          (§16)
-             (NStepReplaySampler with n_step > 1 or recency > 0: n-step returns, recency-weighted draws, §22)
+             (NStepReplaySampler with n_step > 1 or recency > 0: n-step returns, recency-weighted draws, §22;
+              PrioritizedReplaySampler with prioritized=alpha: proportional draws, |q - y| fed back as priorities, §23)
     target   FusedTarget: next action, target critic, y                    (§13)
     critic   FusedCriticLoss into .grad, FusedAdam step                    (§14, §15)
     actor    FusedPolicyGrad into .grad, FusedAdam step, soft updates      (§17, §18, §15)
@@ -36,6 +37,7 @@ from .fused_optim import FusedAdam, soft_update
 from .fused_policy_grad import FusedPolicyGrad
 from .fused_replay import FusedReplaySampler
 from .fused_replay_nstep import NStepReplaySampler, check_n_step
+from .prioritized_replay import PrioritizedReplaySampler, check_prioritized
 from .replay import DeviceReplay
 
 LOG_COLUMNS = _actor_lib.LEARNER_LOG_COLUMNS
@@ -83,8 +85,15 @@ class _FusedLearner:
     kind = None
     _noises = 0          # [B, 2] standard-normal tensors one update consumes
 
-    def _setup(self, device, generator, log_capacity, memory, n_step=1, recency=0.0):
+    def _setup(self, device, generator, log_capacity, memory, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6):
         self.n_step, self.recency = check_n_step(n_step, recency, type(self).__name__)
+        self.prioritized = self.per_eps = None
+        if prioritized is not None:
+            self.prioritized, self.per_eps = check_prioritized(prioritized, per_eps, type(self).__name__)
+            if self.n_step != 1 or self.recency != 0.0:
+                raise ValueError(f"uavx: {type(self).__name__} draws prioritized batches one step at a time: prioritized="
+                                 f"{prioritized} goes with n_step=1 and recency=0, not n_step={self.n_step}, "
+                                 f"recency={self.recency}")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"uavx: the learners need a GPU (cuda:N), got {self.device}: there is no CPU path")
@@ -104,6 +113,7 @@ class _FusedLearner:
         self.updates = 0                  # the host's count of updates enqueued: what `updates=None` stands for
         self._losses_in = (ctypes.c_void_p * 3)()
         self._sampler = self._batch = self._y = None
+        self._qbuf = {}       # rows -> (q [towers, rows], dq/da [towers, rows, 2]) of the priority feedback
         self._graphs = None
         self.memory = None
         if memory is not None:
@@ -121,8 +131,37 @@ class _FusedLearner:
     def _full(self, updates):
         return True
 
-    def _update(self, s, a, r, s2, mask, noise, full):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None):
         raise NotImplementedError
+
+    # ---- priorities ---------------------------------------------------------------------------------------------------
+    def _q_out(self, rows):
+        """The feedback's (q, dq/da) buffers for `rows` rows: reserved ones, or new ones outside a capture."""
+        if rows not in self._qbuf:
+            capture_guard("buffers", rows)
+            towers = self._pgrad.critic.critic.towers
+            self._qbuf[rows] = (torch.empty((towers, rows), dtype=torch.float32, device=self.device),
+                                torch.empty((towers, rows, 2), dtype=torch.float32, device=self.device))
+        return self._qbuf[rows]
+
+    def _check_key(self, key, rows):
+        """What update_batch refuses about its keys, before the update computes or draws anything."""
+        if not isinstance(self._sampler, PrioritizedReplaySampler):
+            raise ValueError(f"uavx: keys need a {type(self).__name__} built with prioritized=alpha and a DeviceReplay")
+        if (not torch.is_tensor(key) or key.dtype != torch.int64 or tuple(key.shape) != (rows,) or key.device != self.device
+                or not key.is_contiguous()):
+            raise ValueError(f"uavx: key must be a contiguous int64 tensor of shape [{rows}] on {self.device}")
+
+    def _feedback(self, s, a, y, key):
+        """Between the target and the critic's step: q(s, a) of the LIVE critic (FusedActionGrad.q_dqda, one launch) and
+        max over its towers of |q - y| into the priorities of the sampled transitions.  key: None (nothing happens), or
+        (the sampler's keys, whether the kernels read the ring's fill from the device count)."""
+        if key is None:
+            return
+        key, device_count = key
+        out = self._q_out(s.shape[0])
+        self._pgrad.critic.q_dqda(s, a, out=out)
+        self._sampler.update_priorities(key, out[0], y, device_count=device_count)
 
     # ---- the tail -----------------------------------------------------------------------------------------------------
     def _tail(self, critic_loss, actor_loss, sac=None):
@@ -192,17 +231,23 @@ class _FusedLearner:
             self._y = torch.empty((rows, 1), dtype=torch.float32, device=self.device)
         if self._sampler is not None:
             self._sampler.reserve(rows)
+        if self.prioritized is not None:
+            self._q_out(rows)
         return self
 
-    def update_batch(self, s, a, r, s2, mask, noise=None, updates=None):
+    def update_batch(self, s, a, r, s2, mask, noise=None, updates=None, key=None):
         """One update of the reference's update_parameters on the given device tensors: state [B, 10], action [B, 2],
         reward and mask [B] or [B, 1], next_state [B, 10].  noise: the standard-normal draws of the update as [B, 2] device
         tensors -- SAC (target's, policy's), TD3 the target's, DDPG none; None draws them from the learner's generator.
         updates: the reference's `updates` argument (TD3's policy_freq, SAC's target_update_interval); None = the number of
-        updates run so far.  Returns nothing: the numbers are in the loss ring (losses())."""
+        updates run so far.  key: the [B] int64 keys a PrioritizedReplaySampler returned with the batch: the update then
+        feeds |q - y| back as their priorities; None leaves the priorities alone.  Returns nothing: the numbers are in the
+        loss ring (losses())."""
         rows, noise = self._check_batch(s, a, r, s2, mask, noise)
+        if key is not None:
+            self._check_key(key, rows)
         u = self.updates if updates is None else int(updates)
-        self._update(s, a, r, s2, mask, noise, self._full(u))
+        self._update(s, a, r, s2, mask, noise, self._full(u), None if key is None else (key, False))
         self.updates += 1
 
     def _discount(self):
@@ -210,11 +255,15 @@ class _FusedLearner:
 
     def attach(self, memory):
         """The DeviceReplay that update_parameters(None, ...) and capture() sample from: through a FusedReplaySampler, or,
-        for a learner built with n_step > 1 or recency > 0, through an NStepReplaySampler with the learner's discount."""
+        for a learner built with n_step > 1 or recency > 0, through an NStepReplaySampler with the learner's discount, or,
+        for one built with prioritized=alpha, through a PrioritizedReplaySampler with beta = 0 (the critic loss takes no
+        per-row weight)."""
         if not isinstance(memory, DeviceReplay):
             raise TypeError(f"uavx: the learners sample from a DeviceReplay, not {type(memory).__name__}")
         if self.memory is not memory:
-            if self.n_step == 1 and self.recency == 0.0:
+            if self.prioritized is not None:
+                sampler = PrioritizedReplaySampler(memory, alpha=self.prioritized, beta=0.0, eps=self.per_eps)
+            elif self.n_step == 1 and self.recency == 0.0:
                 sampler = FusedReplaySampler(memory)
             else:           # the walk discounts with the learner's own discount, so that y = R + discount^len * mask' * (...)
                 sampler = NStepReplaySampler(memory, n_step=self.n_step, gamma=self._discount(), recency=self.recency)
@@ -238,7 +287,11 @@ class _FusedLearner:
                 self.attach(memory)
             if self._sampler is None:
                 raise ValueError("uavx: update_parameters needs a DeviceReplay (or attach() one first)")
-            s, a, r, s2, mask = self._sampler.sample(int(batch_size), generator=self.generator)
+            batch = self._sampler.sample(int(batch_size), generator=self.generator)
+            if self.prioritized is not None:         # (..., weight, key): the weight is not used (beta = 0)
+                self.update_batch(*batch[:5], updates=updates, key=batch[6])
+                return
+            s, a, r, s2, mask = batch
         self.update_batch(s, a, r, s2, mask, updates=updates)
 
     # ---- capture / run ------------------------------------------------------------------------------------------------
@@ -269,7 +322,9 @@ class _FusedLearner:
             batch = sampler.sample(rows, generator=gen)
             warm = self._throwaway()
             for full in self._variants():
-                warm._update(*batch, (None,) * self._noises, full)
+                warm._update(*batch[:5], (None,) * self._noises, full)
+            if self.prioritized is not None:         # the feedback's kernels, on keys of -1: nothing is written
+                self._feedback(batch[0], batch[1], self._target_out(rows), (sampler._none[rows], False))
             torch.cuda.synchronize(dev)
             warm.close()
         torch.cuda.current_stream(dev).wait_stream(side)
@@ -283,7 +338,7 @@ class _FusedLearner:
                 g.register_generator_state(gen)
             with torch.cuda.graph(g):
                 b = sampler.sample(rows, generator=gen, out=self._batch, device_count=True)
-                self._update(*b, (None,) * self._noises, full)
+                self._update(*b[:5], (None,) * self._noises, full, (b[6], True) if self.prioritized is not None else None)
             graphs[full] = g
         self._graphs = graphs
         return self
@@ -356,13 +411,13 @@ class FusedSAC(_FusedLearner):
 
     def __init__(self, n_states=10, n_actions=2, lr=3e-4, tau=5e-3, gamma=0.99, alpah=2, target_update_interval=1,
                  automatic_entropy_tuning=True, target_entropy=None, device="cuda", generator=None, log_capacity=1024,
-                 memory=None, hidden=256, n_step=1, recency=0.0):
+                 memory=None, hidden=256, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6):
         self.lr, self.tau, self.gamma = lr, tau, gamma
         self.target_update_interval = int(target_update_interval)
         if self.target_update_interval < 1:
             raise ValueError(f"uavx: target_update_interval must be >= 1, got {target_update_interval}")
         self.automatic_entropy_tuning = bool(automatic_entropy_tuning)
-        self._setup(device, generator, log_capacity, memory, n_step, recency)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden=hidden)
         self.critic = policy.TwinQ(n_states, n_actions, hidden).to(dev)
@@ -411,9 +466,10 @@ class FusedSAC(_FusedLearner):
     def _full(self, updates):
         return updates % self.target_update_interval == 0
 
-    def _update(self, s, a, r, s2, mask, noise, full):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None):
         gen = self.generator
         y = self._target(s2, r, mask, alpha=self._alpha, generator=gen, noise=noise[0], out=self._target_out(s.shape[0]))
+        self._feedback(s, a, y, key)
         critic_loss = self._closs.backward(s, a, y)
         # the soft update reads only the critic: it rides in the critic's step, and the packed target follows it
         self._critic_adam.step(update_target=full, refresh=self._target_h if full else None)
@@ -537,13 +593,13 @@ class FusedTD3(_ActorCriticLearner):
 
     def __init__(self, state_dim=10, action_dim=2, discount=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
                  policy_freq=2, device="cuda", generator=None, log_capacity=1024, memory=None, hidden=256, n_step=1,
-                 recency=0.0):
+                 recency=0.0, prioritized=None, per_eps=1e-6):
         self.discount, self.tau, self.policy_noise, self.noise_clip = discount, tau, policy_noise, noise_clip
         self.policy_freq = int(policy_freq)
         if self.policy_freq < 1:
             raise ValueError(f"uavx: policy_freq must be >= 1, got {policy_freq}")
         self.max_action = 1
-        self._setup(device, generator, log_capacity, memory, n_step, recency)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps)
         dev = self.device
         self._dims = dict(state_dim=state_dim, action_dim=action_dim, hidden=hidden)
         self.actor = policy.TD3Actor(state_dim, action_dim, hidden).to(dev)
@@ -566,8 +622,9 @@ class FusedTD3(_ActorCriticLearner):
     def _full(self, updates):
         return updates % self.policy_freq == 0
 
-    def _update(self, s, a, r, s2, mask, noise, full):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None):
         y = self._target(s2, r, mask, generator=self.generator, noise=noise[0], out=self._target_out(s.shape[0]))
+        self._feedback(s, a, y, key)
         critic_loss = self._closs.backward(s, a, y)
         self._critic_adam.step(update_target=False)
         self._tail(critic_loss, self._actor_and_targets(s) if full else None)
@@ -614,10 +671,10 @@ class FusedDDPG(_ActorCriticLearner):
 
     def __init__(self, n_states=10, n_actions=2, noise_std_dev=0.2, actor_lr=1e-4, critic_lr=1e-3, tau=5e-3, gamma=0.99,
                  device="cuda", generator=None, log_capacity=1024, memory=None, hidden1=400, hidden2=300, n_step=1,
-                 recency=0.0):
+                 recency=0.0, prioritized=None, per_eps=1e-6):
         self.n_states, self.n_actions = n_states, n_actions
         self.noise_std_dev, self.tau, self.gamma = float(noise_std_dev), tau, gamma
-        self._setup(device, generator, log_capacity, memory, n_step, recency)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden1=hidden1, hidden2=hidden2)
         self.actor = ddpg_init(policy.DDPGActor(n_states, n_actions, hidden1, hidden2), 5e-4).to(dev)     # model.py:8,19-22
@@ -631,8 +688,9 @@ class FusedDDPG(_ActorCriticLearner):
         self._gamma = gamma
         self._build()
 
-    def _update(self, s, a, r, s2, mask, noise, full):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None):
         y = self._target(s2, r, mask, out=self._target_out(s.shape[0]))
+        self._feedback(s, a, y, key)
         critic_loss = self._closs.backward(s, a, y)
         self._critic_adam.step(update_target=False)
         self._tail(critic_loss, self._actor_and_targets(s))
