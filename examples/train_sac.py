@@ -31,7 +31,13 @@ ap.add_argument("--n-step", type=int, default=1, help="steps of return summed pe
 ap.add_argument("--recency", type=float, default=0.0, help="share of rows drawn with a weight that grows with recency")
 ap.add_argument("--prioritized", type=float, default=None, metavar="ALPHA",
                 help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency")
+ap.add_argument("--per-beta", type=float, default=0.0, metavar="B0",
+                help="importance-sampling exponent of the prioritized critic loss at the start (DESIGN.md §24); 0: unweighted")
+ap.add_argument("--per-beta-final", type=float, default=None, metavar="B1",
+                help="anneal the exponent linearly to this value over the run (default: keep B0)")
 args = ap.parse_args()
+if args.per_beta_final is not None and not args.per_beta > 0:
+    ap.error("--per-beta-final anneals a weighted loss: give --per-beta B0 > 0 with it")
 
 dev = torch.device("cuda", 0)
 venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=0)
@@ -39,7 +45,7 @@ mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
 gen = torch.Generator(device=dev).manual_seed(0)
 agent = FusedSAC(device=dev, generator=gen, memory=mem, n_step=args.n_step, recency=args.recency,
-                 prioritized=args.prioritized)
+                 prioritized=args.prioritized, per_beta=args.per_beta)
 
 t0 = time.perf_counter()
 for t in range(args.steps):
@@ -48,6 +54,8 @@ for t in range(args.steps):
     if t + 1 == args.start_steps:
         agent.capture(args.batch)                                              # sampling + the whole update, one graph
     if t + 1 >= args.start_steps:
+        if args.per_beta_final is not None:                                    # a device slot: the captured update follows it
+            agent.set_per_beta(args.per_beta + (args.per_beta_final - args.per_beta) * t / max(1, args.steps - 1))
         agent.run(args.updates_per_step)
     if (t + 1) % args.report == 0 and agent.updates:
         q1, q2, pi, al, alpha = agent.losses(last=1)[0, :5]                    # the one host read

@@ -21,7 +21,7 @@ import ctypes
 
 import torch
 
-from . import _actor_lib
+from . import _actor_lib, _wgrad_lib
 from ._fused_common import (KIND_NAMES, PRECISIONS, ParamSlots, Workspace, actor_layers, alpha_arg, check_buffers,
                             check_on_gpu, check_packable, column, critic_layers, noise_arg, pack_pointers, rows2,
                             stream)
@@ -217,6 +217,7 @@ class FusedCriticLoss:
         l1, l2 = closs.backward(s, a, y)          # SAC / TD3: mse_loss(q1, y) + mse_loss(q2, y); DDPG: one L1 loss
         critic_optim.step()
         closs.reserve(rows)                       # sizes the workspace before a graph capture
+        closs.backward(s, a, y, weight=w, q_out=q)   # prioritized replay: mean(w * loss) and q(s, a) [towers, B] (§24)
 
     loss: "mse" (sac.py, td3.py), "l1" (ddpg.py:68) or None for the learner's own.  The call reads the module's LIVE
     parameters when the kernels run (no refresh(): an optimiser step is seen by the next call), and leaves the packed
@@ -237,6 +238,7 @@ class FusedCriticLoss:
         self._slots = ParamSlots((p for lin in fc._layers for p in (lin.weight, lin.bias)), 12, "FusedCriticLoss", "critic")
         self._loss = torch.zeros(fc.towers, dtype=torch.float32, device=self.device)
         self._ws = Workspace(self.device)
+        self._wlib = None
 
     def workspace_bytes(self, rows):
         n = ctypes.c_int64()
@@ -245,14 +247,31 @@ class FusedCriticLoss:
         return n.value
 
     def reserve(self, rows):
-        """Grows the workspace to what `rows` rows need (a graph capture cannot allocate it)."""
+        """Grows the workspace to what `rows` rows need (a graph capture cannot allocate it).  One workspace serves the
+        unweighted and the weighted call: for the same critic and rows the two libraries ask for the same layout."""
         self._ws.reserve(self.workspace_bytes(rows))
         return self
 
-    def backward(self, state, action, y):
+    def _weighted(self):
+        """libuavx_wgrad.so, loaded by the first call that passes a weight or asks for q."""
+        if self._wlib is None:
+            if self.critic.precision != "f32":
+                raise RuntimeError(f"uavx: the weighted critic gradient has no kernel compiled for a "
+                                   f"{self.critic.precision} FusedCritic (f32 only)")
+            self._wlib = _wgrad_lib.load()
+        return self._wlib
+
+    def backward(self, state, action, y, weight=None, q_out=None):
         """Overwrites every critic parameter's .grad with the gradient of the loss on [B, 10] states, [B, 2] actions
         (any row stride) and targets y ([B] or [B, 1], any stride); returns the loss of each tower as 0-d device tensors
-        (l1, l2), or the one loss of a DDPG critic."""
+        (l1, l2), or the one loss of a DDPG critic.
+
+        weight: per-row importance-sampling weights w ([B] or [B, 1] float32, any positive stride; finite and >= 0, which
+        is not checked on the device): the loss becomes mean_b w_b (q - y)^2, or mean_b w_b |q - y|.  q_out: a contiguous
+        [towers, B] float32 tensor that receives q(s, a) of the live critic, what a prioritized sampler's
+        update_priorities takes.  With either given the call goes to libuavx_wgrad.so (include/uavx_wcritic_grad.h, three
+        launches as well); weight=None there stands for a weight of 1, which gives the unweighted gradients bit for bit.
+        With both None the call is the unweighted one of libuavx_actor.so."""
         dev = self.device
         rows, s_stride = rows2(state, self.critic.obs_dim, dev, "state")
         arows, a_stride = rows2(action, self.critic.act_dim, dev, "action")
@@ -261,13 +280,33 @@ class FusedCriticLoss:
         y_stride = column(y, rows, dev, "y")
         if rows < 1 or rows > _actor_lib.GRAD_MAX_ROWS:
             raise ValueError(f"uavx: FusedCriticLoss takes 1..{_actor_lib.GRAD_MAX_ROWS} rows, got {rows}")
+        weighted = weight is not None or q_out is not None
+        w_ptr, w_stride, q_ptr = None, 1, None
+        if weight is not None:
+            w_stride = column(weight, rows, dev, "weight")
+            if w_stride < 1:
+                raise ValueError("uavx: weight must have a positive row stride")
+            w_ptr = weight.data_ptr()
+        if q_out is not None:
+            check_buffers(((q_out, (self.critic.towers, rows), "q_out"),), dev)
+            q_ptr = q_out.data_ptr()
+        wlib = self._weighted() if weighted else None
         pptrs = self._slots.fill_params(dev)
         self._ws.ensure(self.workspace_bytes(rows), rows)
         ws = self._ws.buf
-        rc = self._lib.uavx_critic_grad(self.critic._h, _LOSSES[self.loss], pptrs, state.data_ptr(), rows, s_stride,
-                                        action.data_ptr(), a_stride, y.data_ptr(), y_stride, self._slots.fill_grads(),
-                                        self._loss.data_ptr(), ws.data_ptr(), ws.numel(), stream(dev))
-        _actor_lib.check_critic(rc, "uavx_critic_grad")
+        if not weighted:
+            rc = self._lib.uavx_critic_grad(self.critic._h, _LOSSES[self.loss], pptrs, state.data_ptr(), rows, s_stride,
+                                            action.data_ptr(), a_stride, y.data_ptr(), y_stride, self._slots.fill_grads(),
+                                            self._loss.data_ptr(), ws.data_ptr(), ws.numel(), stream(dev))
+            _actor_lib.check_critic(rc, "uavx_critic_grad")
+        else:
+            fc = self.critic
+            with torch.cuda.device(dev):
+                rc = wlib.uavx_wcritic_grad(self.kind, fc.hidden1, fc.hidden2, fc.towers, _LOSSES[self.loss], pptrs,
+                                            state.data_ptr(), rows, s_stride, action.data_ptr(), a_stride, y.data_ptr(),
+                                            y_stride, w_ptr, w_stride, self._slots.fill_grads(), self._loss.data_ptr(),
+                                            q_ptr, ws.data_ptr(), ws.numel(), stream(dev))
+            _wgrad_lib.check(rc, "uavx_wcritic_grad")
         return (self._loss[0], self._loss[1]) if self.critic.towers == 2 else self._loss[0]
 
     def close(self):

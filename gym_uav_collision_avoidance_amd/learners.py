@@ -3,7 +3,8 @@ pytorch_ddpg_temp/ddpg.py) with every step of update_parameters as HIP launches 
 
     sample   FusedReplaySampler on a DeviceReplay                          (§16)
              (NStepReplaySampler with n_step > 1 or recency > 0: n-step returns, recency-weighted draws, §22;
-              PrioritizedReplaySampler with prioritized=alpha: proportional draws, |q - y| fed back as priorities, §23)
+              PrioritizedReplaySampler with prioritized=alpha: proportional draws, |q - y| fed back as priorities, §23;
+              with per_beta > 0 its importance-sampling weights multiply the critic loss row by row, §24)
     target   FusedTarget: next action, target critic, y                    (§13)
     critic   FusedCriticLoss into .grad, FusedAdam step                    (§14, §15)
     actor    FusedPolicyGrad into .grad, FusedAdam step, soft updates      (§17, §18, §15)
@@ -85,7 +86,8 @@ class _FusedLearner:
     kind = None
     _noises = 0          # [B, 2] standard-normal tensors one update consumes
 
-    def _setup(self, device, generator, log_capacity, memory, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6):
+    def _setup(self, device, generator, log_capacity, memory, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6,
+               per_beta=0.0):
         self.n_step, self.recency = check_n_step(n_step, recency, type(self).__name__)
         self.prioritized = self.per_eps = None
         if prioritized is not None:
@@ -94,6 +96,12 @@ class _FusedLearner:
                 raise ValueError(f"uavx: {type(self).__name__} draws prioritized batches one step at a time: prioritized="
                                  f"{prioritized} goes with n_step=1 and recency=0, not n_step={self.n_step}, "
                                  f"recency={self.recency}")
+        self.per_beta = self._check_per_beta(per_beta)
+        if self.per_beta > 0.0 and self.prioritized is None:
+            raise ValueError(f"uavx: {type(self).__name__} weights the critic loss of prioritized batches: per_beta="
+                             f"{per_beta} needs prioritized=alpha")
+        # per_beta > 0 at construction picks the weighted update (§24) for the learner's life; set_per_beta moves beta in it
+        self._per_weighted = self.per_beta > 0.0
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"uavx: the learners need a GPU (cuda:N), got {self.device}: there is no CPU path")
@@ -131,16 +139,42 @@ class _FusedLearner:
     def _full(self, updates):
         return True
 
-    def _update(self, s, a, r, s2, mask, noise, full, key=None):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None, weight=None):
         raise NotImplementedError
 
     # ---- priorities ---------------------------------------------------------------------------------------------------
+    def _check_per_beta(self, beta):
+        """The importance-sampling exponent as a float: finite, in [0, 1]."""
+        try:
+            b = float(beta)
+        except (TypeError, ValueError):
+            b = float("nan")                 # refused below
+        if not 0.0 <= b <= 1.0:
+            raise ValueError(f"uavx: {type(self).__name__} takes an importance-sampling exponent per_beta in [0, 1], got "
+                             f"{beta}")
+        return b
+
+    def set_per_beta(self, beta):
+        """Moves the importance-sampling exponent of a learner built with per_beta > 0 (an annealed beta): the sampler
+        keeps it in a device slot, so a captured update follows it.  A learner built with per_beta == 0 runs the
+        unweighted update, which reads no weights, and refuses."""
+        beta = self._check_per_beta(beta)
+        if not self._per_weighted:
+            raise ValueError(f"uavx: set_per_beta needs a {type(self).__name__} built with prioritized=alpha and "
+                             f"per_beta > 0: this one runs the unweighted update")
+        self.per_beta = beta
+        if self._sampler is not None:
+            self._sampler.set_beta(beta)
+        return self
+
     def _q_out(self, rows):
-        """The feedback's (q, dq/da) buffers for `rows` rows: reserved ones, or new ones outside a capture."""
+        """The feedback's (q, dq/da) buffers for `rows` rows: reserved ones, or new ones outside a capture.  The weighted
+        update takes q from the critic gradient itself and has no dq/da (None)."""
         if rows not in self._qbuf:
             capture_guard("buffers", rows)
             towers = self._pgrad.critic.critic.towers
             self._qbuf[rows] = (torch.empty((towers, rows), dtype=torch.float32, device=self.device),
+                                None if self._per_weighted else
                                 torch.empty((towers, rows, 2), dtype=torch.float32, device=self.device))
         return self._qbuf[rows]
 
@@ -162,6 +196,19 @@ class _FusedLearner:
         out = self._q_out(s.shape[0])
         self._pgrad.critic.q_dqda(s, a, out=out)
         self._sampler.update_priorities(key, out[0], y, device_count=device_count)
+
+    def _critic_grad(self, s, a, y, key, weight):
+        """The priority feedback and the critic gradient of one update -> the critic loss.  Without a weight, in a learner
+        built with per_beta == 0: _feedback, then the unweighted gradient.  Otherwise (§24) the weighted gradient, whose row
+        pass hands back q(s, a) of the live critic for update_priorities: no q_dqda launch."""
+        if weight is None and not self._per_weighted:
+            self._feedback(s, a, y, key)
+            return self._closs.backward(s, a, y)
+        q = None if key is None else self._q_out(s.shape[0])[0]
+        loss = self._closs.backward(s, a, y, weight=weight, q_out=q)
+        if key is not None:
+            self._sampler.update_priorities(key[0], q, y, device_count=key[1])
+        return loss
 
     # ---- the tail -----------------------------------------------------------------------------------------------------
     def _tail(self, critic_loss, actor_loss, sac=None):
@@ -235,19 +282,23 @@ class _FusedLearner:
             self._q_out(rows)
         return self
 
-    def update_batch(self, s, a, r, s2, mask, noise=None, updates=None, key=None):
+    def update_batch(self, s, a, r, s2, mask, noise=None, updates=None, key=None, weight=None):
         """One update of the reference's update_parameters on the given device tensors: state [B, 10], action [B, 2],
         reward and mask [B] or [B, 1], next_state [B, 10].  noise: the standard-normal draws of the update as [B, 2] device
         tensors -- SAC (target's, policy's), TD3 the target's, DDPG none; None draws them from the learner's generator.
         updates: the reference's `updates` argument (TD3's policy_freq, SAC's target_update_interval); None = the number of
         updates run so far.  key: the [B] int64 keys a PrioritizedReplaySampler returned with the batch: the update then
-        feeds |q - y| back as their priorities; None leaves the priorities alone.  Returns nothing: the numbers are in the
-        loss ring (losses())."""
+        feeds |q - y| back as their priorities; None leaves the priorities alone.  weight: importance-sampling weights
+        ([B] or [B, 1] float32, finite and >= 0, e.g. the sampler's) that multiply each row's critic loss (§24); a weight
+        without a key weights the loss and leaves the priorities alone.  Returns nothing: the numbers are in the loss ring
+        (losses())."""
         rows, noise = self._check_batch(s, a, r, s2, mask, noise)
         if key is not None:
             self._check_key(key, rows)
+        if weight is not None and column(weight, rows, self.device, "weight") < 1:
+            raise ValueError("uavx: weight must have a positive row stride")
         u = self.updates if updates is None else int(updates)
-        self._update(s, a, r, s2, mask, noise, self._full(u), None if key is None else (key, False))
+        self._update(s, a, r, s2, mask, noise, self._full(u), None if key is None else (key, False), weight)
         self.updates += 1
 
     def _discount(self):
@@ -256,13 +307,13 @@ class _FusedLearner:
     def attach(self, memory):
         """The DeviceReplay that update_parameters(None, ...) and capture() sample from: through a FusedReplaySampler, or,
         for a learner built with n_step > 1 or recency > 0, through an NStepReplaySampler with the learner's discount, or,
-        for one built with prioritized=alpha, through a PrioritizedReplaySampler with beta = 0 (the critic loss takes no
-        per-row weight)."""
+        for one built with prioritized=alpha, through a PrioritizedReplaySampler with beta = per_beta (0: every weight is
+        1 and the update does not read them)."""
         if not isinstance(memory, DeviceReplay):
             raise TypeError(f"uavx: the learners sample from a DeviceReplay, not {type(memory).__name__}")
         if self.memory is not memory:
             if self.prioritized is not None:
-                sampler = PrioritizedReplaySampler(memory, alpha=self.prioritized, beta=0.0, eps=self.per_eps)
+                sampler = PrioritizedReplaySampler(memory, alpha=self.prioritized, beta=self.per_beta, eps=self.per_eps)
             elif self.n_step == 1 and self.recency == 0.0:
                 sampler = FusedReplaySampler(memory)
             else:           # the walk discounts with the learner's own discount, so that y = R + discount^len * mask' * (...)
@@ -288,8 +339,9 @@ class _FusedLearner:
             if self._sampler is None:
                 raise ValueError("uavx: update_parameters needs a DeviceReplay (or attach() one first)")
             batch = self._sampler.sample(int(batch_size), generator=self.generator)
-            if self.prioritized is not None:         # (..., weight, key): the weight is not used (beta = 0)
-                self.update_batch(*batch[:5], updates=updates, key=batch[6])
+            if self.prioritized is not None:         # (..., weight, key): with per_beta == 0 the weight is 1 and not read
+                self.update_batch(*batch[:5], updates=updates, key=batch[6],
+                                  weight=batch[5] if self._per_weighted else None)
                 return
             s, a, r, s2, mask = batch
         self.update_batch(s, a, r, s2, mask, updates=updates)
@@ -323,7 +375,12 @@ class _FusedLearner:
             warm = self._throwaway()
             for full in self._variants():
                 warm._update(*batch[:5], (None,) * self._noises, full)
-            if self.prioritized is not None:         # the feedback's kernels, on keys of -1: nothing is written
+            if self._per_weighted:                   # the weighted gradient's kernels, into the throw-away critic's .grad,
+                y = self._target_out(rows)           # and the feedback's on keys of -1: nothing is written
+                q = self._q_out(rows)[0]
+                warm._closs.backward(batch[0], batch[1], y, weight=batch[5], q_out=q)
+                sampler.update_priorities(sampler._none[rows], q, y)
+            elif self.prioritized is not None:       # the feedback's kernels, on keys of -1: nothing is written
                 self._feedback(batch[0], batch[1], self._target_out(rows), (sampler._none[rows], False))
             torch.cuda.synchronize(dev)
             warm.close()
@@ -338,7 +395,8 @@ class _FusedLearner:
                 g.register_generator_state(gen)
             with torch.cuda.graph(g):
                 b = sampler.sample(rows, generator=gen, out=self._batch, device_count=True)
-                self._update(*b[:5], (None,) * self._noises, full, (b[6], True) if self.prioritized is not None else None)
+                self._update(*b[:5], (None,) * self._noises, full, (b[6], True) if self.prioritized is not None else None,
+                             b[5] if self._per_weighted else None)
             graphs[full] = g
         self._graphs = graphs
         return self
@@ -411,13 +469,13 @@ class FusedSAC(_FusedLearner):
 
     def __init__(self, n_states=10, n_actions=2, lr=3e-4, tau=5e-3, gamma=0.99, alpah=2, target_update_interval=1,
                  automatic_entropy_tuning=True, target_entropy=None, device="cuda", generator=None, log_capacity=1024,
-                 memory=None, hidden=256, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6):
+                 memory=None, hidden=256, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0):
         self.lr, self.tau, self.gamma = lr, tau, gamma
         self.target_update_interval = int(target_update_interval)
         if self.target_update_interval < 1:
             raise ValueError(f"uavx: target_update_interval must be >= 1, got {target_update_interval}")
         self.automatic_entropy_tuning = bool(automatic_entropy_tuning)
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden=hidden)
         self.critic = policy.TwinQ(n_states, n_actions, hidden).to(dev)
@@ -466,11 +524,10 @@ class FusedSAC(_FusedLearner):
     def _full(self, updates):
         return updates % self.target_update_interval == 0
 
-    def _update(self, s, a, r, s2, mask, noise, full, key=None):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None, weight=None):
         gen = self.generator
         y = self._target(s2, r, mask, alpha=self._alpha, generator=gen, noise=noise[0], out=self._target_out(s.shape[0]))
-        self._feedback(s, a, y, key)
-        critic_loss = self._closs.backward(s, a, y)
+        critic_loss = self._critic_grad(s, a, y, key, weight)
         # the soft update reads only the critic: it rides in the critic's step, and the packed target follows it
         self._critic_adam.step(update_target=full, refresh=self._target_h if full else None)
         policy_loss, _ = self._pgrad.backward(s, alpha=self._alpha, noise=noise[1], generator=gen)
@@ -593,13 +650,13 @@ class FusedTD3(_ActorCriticLearner):
 
     def __init__(self, state_dim=10, action_dim=2, discount=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
                  policy_freq=2, device="cuda", generator=None, log_capacity=1024, memory=None, hidden=256, n_step=1,
-                 recency=0.0, prioritized=None, per_eps=1e-6):
+                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0):
         self.discount, self.tau, self.policy_noise, self.noise_clip = discount, tau, policy_noise, noise_clip
         self.policy_freq = int(policy_freq)
         if self.policy_freq < 1:
             raise ValueError(f"uavx: policy_freq must be >= 1, got {policy_freq}")
         self.max_action = 1
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta)
         dev = self.device
         self._dims = dict(state_dim=state_dim, action_dim=action_dim, hidden=hidden)
         self.actor = policy.TD3Actor(state_dim, action_dim, hidden).to(dev)
@@ -622,10 +679,9 @@ class FusedTD3(_ActorCriticLearner):
     def _full(self, updates):
         return updates % self.policy_freq == 0
 
-    def _update(self, s, a, r, s2, mask, noise, full, key=None):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None, weight=None):
         y = self._target(s2, r, mask, generator=self.generator, noise=noise[0], out=self._target_out(s.shape[0]))
-        self._feedback(s, a, y, key)
-        critic_loss = self._closs.backward(s, a, y)
+        critic_loss = self._critic_grad(s, a, y, key, weight)
         self._critic_adam.step(update_target=False)
         self._tail(critic_loss, self._actor_and_targets(s) if full else None)
 
@@ -671,10 +727,10 @@ class FusedDDPG(_ActorCriticLearner):
 
     def __init__(self, n_states=10, n_actions=2, noise_std_dev=0.2, actor_lr=1e-4, critic_lr=1e-3, tau=5e-3, gamma=0.99,
                  device="cuda", generator=None, log_capacity=1024, memory=None, hidden1=400, hidden2=300, n_step=1,
-                 recency=0.0, prioritized=None, per_eps=1e-6):
+                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0):
         self.n_states, self.n_actions = n_states, n_actions
         self.noise_std_dev, self.tau, self.gamma = float(noise_std_dev), tau, gamma
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden1=hidden1, hidden2=hidden2)
         self.actor = ddpg_init(policy.DDPGActor(n_states, n_actions, hidden1, hidden2), 5e-4).to(dev)     # model.py:8,19-22
@@ -688,10 +744,9 @@ class FusedDDPG(_ActorCriticLearner):
         self._gamma = gamma
         self._build()
 
-    def _update(self, s, a, r, s2, mask, noise, full, key=None):
+    def _update(self, s, a, r, s2, mask, noise, full, key=None, weight=None):
         y = self._target(s2, r, mask, out=self._target_out(s.shape[0]))
-        self._feedback(s, a, y, key)
-        critic_loss = self._closs.backward(s, a, y)
+        critic_loss = self._critic_grad(s, a, y, key, weight)
         self._critic_adam.step(update_target=False)
         self._tail(critic_loss, self._actor_and_targets(s))
 
