@@ -33,10 +33,14 @@ ap.add_argument("--updates-per-step", type=int, default=1)
 ap.add_argument("--report", type=int, default=500)
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--checkpoint", type=str, default=None, help="directory to write actor.chpt and critic.chpt into at the end")
-ap.add_argument("--n-step", type=int, default=1, help="steps of return summed per sampled row (1..8)")
+ap.add_argument("--n-step", type=int, default=1,
+                help="steps of return summed per uniformly sampled row (1..8); with --prioritized it is --per-n-step")
 ap.add_argument("--recency", type=float, default=0.0, help="share of rows drawn with a weight that grows with recency")
 ap.add_argument("--prioritized", type=float, default=None, metavar="ALPHA",
-                help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency")
+                help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency: "
+                     "its n-step returns are --per-n-step")
+ap.add_argument("--per-n-step", type=int, default=1, metavar="N",
+                help="steps of return walked from each prioritized draw (1..8, DESIGN.md §25); needs --prioritized")
 ap.add_argument("--per-beta", type=float, default=0.0, metavar="B0",
                 help="importance-sampling exponent of the prioritized critic loss at the start (DESIGN.md §24); 0: unweighted")
 ap.add_argument("--per-beta-final", type=float, default=None, metavar="B1",
@@ -50,7 +54,7 @@ venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=args.see
 mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
 agent = FusedDDPG(noise_std_dev=args.noise_std_dev, device=dev, memory=mem, n_step=args.n_step, recency=args.recency,
-                  prioritized=args.prioritized, per_beta=args.per_beta)
+                  prioritized=args.prioritized, per_beta=args.per_beta, per_n_step=args.per_n_step)
 explore = agent.exploration(mem, seed=args.seed, warmup_steps=args.warmup, reset_on_episode=args.reset_ou_per_episode)
 
 t0 = time.perf_counter()

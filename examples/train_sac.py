@@ -27,10 +27,14 @@ ap.add_argument("--start-steps", type=int, default=16, help="steps collected bef
 ap.add_argument("--updates-per-step", type=int, default=1)
 ap.add_argument("--report", type=int, default=500)
 ap.add_argument("--checkpoint", type=str, default=None, help="directory to write weights.chpt into at the end")
-ap.add_argument("--n-step", type=int, default=1, help="steps of return summed per sampled row (1..8)")
+ap.add_argument("--n-step", type=int, default=1,
+                help="steps of return summed per uniformly sampled row (1..8); with --prioritized it is --per-n-step")
 ap.add_argument("--recency", type=float, default=0.0, help="share of rows drawn with a weight that grows with recency")
 ap.add_argument("--prioritized", type=float, default=None, metavar="ALPHA",
-                help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency")
+                help="proportional prioritized replay with this exponent (DESIGN.md §23); not with --n-step / --recency: "
+                     "its n-step returns are --per-n-step")
+ap.add_argument("--per-n-step", type=int, default=1, metavar="N",
+                help="steps of return walked from each prioritized draw (1..8, DESIGN.md §25); needs --prioritized")
 ap.add_argument("--per-beta", type=float, default=0.0, metavar="B0",
                 help="importance-sampling exponent of the prioritized critic loss at the start (DESIGN.md §24); 0: unweighted")
 ap.add_argument("--per-beta-final", type=float, default=None, metavar="B1",
@@ -45,7 +49,7 @@ mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
 gen = torch.Generator(device=dev).manual_seed(0)
 agent = FusedSAC(device=dev, generator=gen, memory=mem, n_step=args.n_step, recency=args.recency,
-                 prioritized=args.prioritized, per_beta=args.per_beta)
+                 prioritized=args.prioritized, per_beta=args.per_beta, per_n_step=args.per_n_step)
 
 t0 = time.perf_counter()
 for t in range(args.steps):

@@ -4,7 +4,8 @@ pytorch_ddpg_temp/ddpg.py) with every step of update_parameters as HIP launches 
     sample   FusedReplaySampler on a DeviceReplay                          (§16)
              (NStepReplaySampler with n_step > 1 or recency > 0: n-step returns, recency-weighted draws, §22;
               PrioritizedReplaySampler with prioritized=alpha: proportional draws, |q - y| fed back as priorities, §23;
-              with per_beta > 0 its importance-sampling weights multiply the critic loss row by row, §24)
+              with per_beta > 0 its importance-sampling weights multiply the critic loss row by row, §24;
+              with per_n_step > 1 PrioritizedNStepSampler: n-step returns walked from the drawn transitions, §25)
     target   FusedTarget: next action, target critic, y                    (§13)
     critic   FusedCriticLoss into .grad, FusedAdam step                    (§14, §15)
     actor    FusedPolicyGrad into .grad, FusedAdam step, soft updates      (§17, §18, §15)
@@ -26,6 +27,7 @@ and later updates exp(log_alpha); TD3 steps the actor and both targets only when
 There is NO fallback: anything the kernels do not implement raises before a launch."""
 import ctypes
 import math
+import operator
 import os
 
 import torch
@@ -37,7 +39,8 @@ from .fused_critic import FusedCritic, FusedCriticLoss, FusedTarget
 from .fused_optim import FusedAdam, soft_update
 from .fused_policy_grad import FusedPolicyGrad
 from .fused_replay import FusedReplaySampler
-from .fused_replay_nstep import NStepReplaySampler, check_n_step
+from .fused_replay_nstep import N_STEP_MAX, NStepReplaySampler, check_n_step
+from .prioritized_nstep import PrioritizedNStepSampler
 from .prioritized_replay import PrioritizedReplaySampler, check_prioritized
 from .replay import DeviceReplay
 
@@ -87,7 +90,7 @@ class _FusedLearner:
     _noises = 0          # [B, 2] standard-normal tensors one update consumes
 
     def _setup(self, device, generator, log_capacity, memory, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6,
-               per_beta=0.0):
+               per_beta=0.0, per_n_step=1):
         self.n_step, self.recency = check_n_step(n_step, recency, type(self).__name__)
         self.prioritized = self.per_eps = None
         if prioritized is not None:
@@ -102,6 +105,10 @@ class _FusedLearner:
                              f"{per_beta} needs prioritized=alpha")
         # per_beta > 0 at construction picks the weighted update (§24) for the learner's life; set_per_beta moves beta in it
         self._per_weighted = self.per_beta > 0.0
+        self.per_n_step = self._check_per_n_step(per_n_step)
+        if self.per_n_step > 1 and self.prioritized is None:
+            raise ValueError(f"uavx: {type(self).__name__} walks n steps from the keys of prioritized batches: per_n_step="
+                             f"{per_n_step} needs prioritized=alpha (n_step is the uniform sampler's)")
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError(f"uavx: the learners need a GPU (cuda:N), got {self.device}: there is no CPU path")
@@ -153,6 +160,16 @@ class _FusedLearner:
             raise ValueError(f"uavx: {type(self).__name__} takes an importance-sampling exponent per_beta in [0, 1], got "
                              f"{beta}")
         return b
+
+    def _check_per_n_step(self, n):
+        """The steps a prioritized batch walks from each drawn transition, as an int in 1..8 (a bool is not a count)."""
+        try:
+            k = 0 if isinstance(n, bool) else operator.index(n)
+        except TypeError:
+            k = 0
+        if not 1 <= k <= N_STEP_MAX:
+            raise ValueError(f"uavx: {type(self).__name__} takes per_n_step as an integer in 1..{N_STEP_MAX}, got {n!r}")
+        return k
 
     def set_per_beta(self, beta):
         """Moves the importance-sampling exponent of a learner built with per_beta > 0 (an annealed beta): the sampler
@@ -308,11 +325,15 @@ class _FusedLearner:
         """The DeviceReplay that update_parameters(None, ...) and capture() sample from: through a FusedReplaySampler, or,
         for a learner built with n_step > 1 or recency > 0, through an NStepReplaySampler with the learner's discount, or,
         for one built with prioritized=alpha, through a PrioritizedReplaySampler with beta = per_beta (0: every weight is
-        1 and the update does not read them)."""
+        1 and the update does not read them) -- with per_n_step > 1 through a PrioritizedNStepSampler, which walks that many
+        steps from each drawn transition with the learner's discount (§25)."""
         if not isinstance(memory, DeviceReplay):
             raise TypeError(f"uavx: the learners sample from a DeviceReplay, not {type(memory).__name__}")
         if self.memory is not memory:
-            if self.prioritized is not None:
+            if self.prioritized is not None and self.per_n_step > 1:      # the walk discounts with the learner's discount
+                sampler = PrioritizedNStepSampler(memory, alpha=self.prioritized, beta=self.per_beta, eps=self.per_eps,
+                                                  n_step=self.per_n_step, gamma=self._discount())
+            elif self.prioritized is not None:
                 sampler = PrioritizedReplaySampler(memory, alpha=self.prioritized, beta=self.per_beta, eps=self.per_eps)
             elif self.n_step == 1 and self.recency == 0.0:
                 sampler = FusedReplaySampler(memory)
@@ -469,13 +490,13 @@ class FusedSAC(_FusedLearner):
 
     def __init__(self, n_states=10, n_actions=2, lr=3e-4, tau=5e-3, gamma=0.99, alpah=2, target_update_interval=1,
                  automatic_entropy_tuning=True, target_entropy=None, device="cuda", generator=None, log_capacity=1024,
-                 memory=None, hidden=256, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0):
+                 memory=None, hidden=256, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1):
         self.lr, self.tau, self.gamma = lr, tau, gamma
         self.target_update_interval = int(target_update_interval)
         if self.target_update_interval < 1:
             raise ValueError(f"uavx: target_update_interval must be >= 1, got {target_update_interval}")
         self.automatic_entropy_tuning = bool(automatic_entropy_tuning)
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden=hidden)
         self.critic = policy.TwinQ(n_states, n_actions, hidden).to(dev)
@@ -650,13 +671,13 @@ class FusedTD3(_ActorCriticLearner):
 
     def __init__(self, state_dim=10, action_dim=2, discount=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
                  policy_freq=2, device="cuda", generator=None, log_capacity=1024, memory=None, hidden=256, n_step=1,
-                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0):
+                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1):
         self.discount, self.tau, self.policy_noise, self.noise_clip = discount, tau, policy_noise, noise_clip
         self.policy_freq = int(policy_freq)
         if self.policy_freq < 1:
             raise ValueError(f"uavx: policy_freq must be >= 1, got {policy_freq}")
         self.max_action = 1
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step)
         dev = self.device
         self._dims = dict(state_dim=state_dim, action_dim=action_dim, hidden=hidden)
         self.actor = policy.TD3Actor(state_dim, action_dim, hidden).to(dev)
@@ -727,10 +748,10 @@ class FusedDDPG(_ActorCriticLearner):
 
     def __init__(self, n_states=10, n_actions=2, noise_std_dev=0.2, actor_lr=1e-4, critic_lr=1e-3, tau=5e-3, gamma=0.99,
                  device="cuda", generator=None, log_capacity=1024, memory=None, hidden1=400, hidden2=300, n_step=1,
-                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0):
+                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1):
         self.n_states, self.n_actions = n_states, n_actions
         self.noise_std_dev, self.tau, self.gamma = float(noise_std_dev), tau, gamma
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden1=hidden1, hidden2=hidden2)
         self.actor = ddpg_init(policy.DDPGActor(n_states, n_actions, hidden1, hidden2), 5e-4).to(dev)     # model.py:8,19-22
