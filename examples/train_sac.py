@@ -39,6 +39,8 @@ ap.add_argument("--per-beta", type=float, default=0.0, metavar="B0",
                 help="importance-sampling exponent of the prioritized critic loss at the start (DESIGN.md §24); 0: unweighted")
 ap.add_argument("--per-beta-final", type=float, default=None, metavar="B1",
                 help="anneal the exponent linearly to this value over the run (default: keep B0)")
+ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
+                help="clip the global gradient norm of the critic's and the actor's optimiser step to X (DESIGN.md §26)")
 args = ap.parse_args()
 if args.per_beta_final is not None and not args.per_beta > 0:
     ap.error("--per-beta-final anneals a weighted loss: give --per-beta B0 > 0 with it")
@@ -49,7 +51,8 @@ mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
 gen = torch.Generator(device=dev).manual_seed(0)
 agent = FusedSAC(device=dev, generator=gen, memory=mem, n_step=args.n_step, recency=args.recency,
-                 prioritized=args.prioritized, per_beta=args.per_beta, per_n_step=args.per_n_step)
+                 prioritized=args.prioritized, per_beta=args.per_beta, per_n_step=args.per_n_step,
+                 max_grad_norm=args.max_grad_norm)
 
 t0 = time.perf_counter()
 for t in range(args.steps):
@@ -62,9 +65,12 @@ for t in range(args.steps):
             agent.set_per_beta(args.per_beta + (args.per_beta_final - args.per_beta) * t / max(1, args.steps - 1))
         agent.run(args.updates_per_step)
     if (t + 1) % args.report == 0 and agent.updates:
-        q1, q2, pi, al, alpha = agent.losses(last=1)[0, :5]                    # the one host read
+        rows, norms = agent.report(last=1)                                     # the one host read
+        clip = "" if norms["critic"] is None else (f", critic grad norm {norms['critic'][0]:.4g} "
+                                                   f"({norms['critic'][2] / agent.updates:.0%} of steps clipped)")
+        q1, q2, pi, al, alpha = rows[0, :5]
         print(f"step {t + 1}: {agent.updates} updates, critic {q1:.4f} {q2:.4f} policy {pi:.4f} alpha_loss {al:.4f} "
-              f"alpha {alpha:.4f}, {(t + 1) * args.envs / (time.perf_counter() - t0):,.0f} env steps/s")
+              f"alpha {alpha:.4f}, {(t + 1) * args.envs / (time.perf_counter() - t0):,.0f} env steps/s{clip}")
 torch.cuda.synchronize()
 st = venv.episode_stats()
 print(f"{int(st['episodes'].sum())} episodes ended: {int(st['reach'].sum())} reached the goal, {int(st['coll'].sum())} collided")

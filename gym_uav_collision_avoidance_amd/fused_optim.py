@@ -14,8 +14,18 @@ writes it back into every state[p]["step"] (one host synchronisation, outside th
 does that first; reload() reads it again after the wrapped optimiser's own load_state_dict.
 
 lr, betas, eps and tau are read from the param group at every call; a captured graph keeps the values of its capture.
+
+    opt = FusedAdam(critic_optim, target=critic_target, max_grad_norm=10.0)      # clips the global gradient norm first
+
+With max_grad_norm the step goes through libuavx_clip.so (include/uavx_clip.h) instead: one norm over every
+gradient of every param group, as torch.nn.utils.clip_grad_norm_(all_params, max_norm), then the same Adam arithmetic on
+g·coef; three launches for one group.  .grad itself is NOT rewritten: opt.clip_coef is what to multiply it by.  The bound
+lives in a device slot (set_max_grad_norm), so a captured step follows it.  Without the keyword nothing differs and the
+library is not even loaded.
 There is NO fallback: anything the kernels do not implement raises before a launch."""
 import ctypes
+import math
+import numbers
 
 import torch
 
@@ -61,6 +71,18 @@ def _check_tensor(t, device, what):
     if t.numel() < 1:
         raise ValueError(f"uavx: {what} is empty")
     return t.device
+
+
+def check_max_grad_norm(x, what="max_grad_norm"):
+    """A clip bound as a float: a finite number > 0 that is still finite and > 0 as a float32 (tensors are refused: the bound
+    is written into a device slot by the host)."""
+    ok = isinstance(x, numbers.Real) and not isinstance(x, bool)
+    if ok:
+        f32 = float(torch.tensor(float(x), dtype=torch.float32))
+        ok = math.isfinite(float(x)) and x > 0 and math.isfinite(f32) and f32 > 0
+    if not ok:
+        raise ValueError(f"uavx: {what} must be a finite float > 0 (or None: no clipping), got {x!r}")
+    return float(x)
 
 
 def _check_tau(tau):
@@ -115,11 +137,20 @@ class FusedAdam:
 
     optimizer: a torch.optim.Adam (not AdamW) with weight_decay = 0, maximize = False, differentiable = False and a float
     lr; its parameters contiguous float32 on one GPU, at most 16 per group.  target: the target network (module or
-    parameters, in the optimiser's parameter order), tau: its soft-update rate."""
+    parameters, in the optimiser's parameter order), tau: its soft-update rate.
 
-    def __init__(self, optimizer, target=None, tau=5e-3):
+    max_grad_norm: None (the default: the step above, nothing else), or a finite float > 0: every step first clips the
+    global gradient norm -- ONE norm over all parameters of all param groups, float64 sums in a fixed order -- to it, as
+    torch.nn.utils.clip_grad_norm_ would, in three launches for one group.  The parameters' .grad is read
+    and NOT rewritten: the step uses g * clip_coef.  grad_norm, clip_coef (0-d float32) and clipped_steps (0-d int64) are
+    device views of the last step's record; reading them synchronises, holding them does not.  record: with max_grad_norm,
+    an 8-byte aligned float32 device tensor of 6 elements to keep that record in (norm, coef, the int64 count, the bound),
+    for a caller that reads it in one copy with data of its own; None allocates one."""
+
+    def __init__(self, optimizer, target=None, tau=5e-3, max_grad_norm=None, record=None):
         if type(optimizer) is not torch.optim.Adam:
             raise TypeError(f"uavx: FusedAdam wraps a torch.optim.Adam, not {type(optimizer).__name__}")
+        self.max_grad_norm = None if max_grad_norm is None else check_max_grad_norm(max_grad_norm)
         self.optimizer = optimizer
         self.tau = _check_tau(tau)
         self._groups = [list(g["params"]) for g in optimizer.param_groups]
@@ -150,7 +181,51 @@ class FusedAdam:
         self._steps = torch.zeros(len(self._groups), dtype=torch.int64, device=dev)
         self._scalars = torch.zeros((len(self._groups), 2), dtype=torch.float32, device=dev)
         self._step_ptr, self._scalar_ptr = self._steps.data_ptr(), self._scalars.data_ptr()
+        self._clip = None
+        if self.max_grad_norm is not None:
+            self._setup_clip(record)
+        elif record is not None:
+            raise ValueError("uavx: record goes with max_grad_norm: this FusedAdam does not clip")
         self.reload()
+
+    def _setup_clip(self, record):
+        """Loads libuavx_clip.so and allocates what a clipped step reads and writes besides the optimiser's state: the
+        record with the slot of the bound behind it (one 24-byte allocation, or `record`) and the workspace of per-block
+        sums (8 bytes per 1024 gradient elements: sized here, so a capture needs no reserve())."""
+        from . import _clip_lib
+        if len(self._groups) > _clip_lib.MAX_GROUPS:
+            raise ValueError(f"uavx: FusedAdam clips over 1..{_clip_lib.MAX_GROUPS} param groups, got {len(self._groups)}")
+        self._clip = _clip_lib
+        self._clip_lib = _clip_lib.load()
+        dev = self.device
+        # norm, coef | clipped (int64) | max_norm, padding
+        if record is None:
+            record = torch.zeros(6, dtype=torch.float32, device=dev)
+        elif (not torch.is_tensor(record) or record.dtype != torch.float32 or tuple(record.shape) != (6,)
+                or record.device != dev or not record.is_contiguous() or record.data_ptr() % 8):
+            raise ValueError(f"uavx: record must be a contiguous float32 tensor of 6 elements on {dev}, 8-byte aligned")
+        self._clip_rec = record.zero_()
+        self.grad_norm, self.clip_coef = self._clip_rec[0], self._clip_rec[1]
+        self.clipped_steps = self._clip_rec[2:4].view(torch.int64)[0]
+        self._clip_rec[1] = 1.0
+        self._clip_rec[4] = self.max_grad_norm
+        self._clip_groups = (_clip_lib.Group * len(self._groups))()
+        for gi, (cg, tab) in enumerate(zip(self._clip_groups, self._tabs)):
+            cg.n, cg.numel = tab.n, ctypes.addressof(tab.numel)
+            cg.step, cg.scalars = self._step_ptr + 8 * gi, self._scalar_ptr + 8 * gi
+        need = ctypes.c_int64()
+        _clip_lib.check(self._clip_lib.uavx_clip_workspace_bytes(len(self._groups), self._clip_groups, ctypes.byref(need)),
+                        "uavx_clip_workspace_bytes")
+        self._clip_work = torch.empty(need.value // 8, dtype=torch.float64, device=dev)
+
+    def set_max_grad_norm(self, max_grad_norm):
+        """Moves the bound of an object built with max_grad_norm: written into the device slot on the current stream, so
+        the next step -- a replay of a captured one included -- clips to it."""
+        if self._clip is None:
+            raise ValueError("uavx: set_max_grad_norm needs a FusedAdam built with max_grad_norm: this one does not clip")
+        self.max_grad_norm = check_max_grad_norm(max_grad_norm)
+        self._clip_rec[4] = self.max_grad_norm
+        return self
 
     @staticmethod
     def _hyper(g):
@@ -271,6 +346,20 @@ class FusedAdam:
                           tab.fill("x", [s["max_exp_avg_sq"] for s in sts]) if g["amsgrad"] else None,
                           tab.fill("t", self._targets[gi]) if update_target else None))
         st = stream(dev)
+        if self._clip is not None:
+            for cg, (gi, tab, (lr, b1, b2, eps), p, g, m, v, x, t) in zip(self._clip_groups, calls):
+                cg.params, cg.grads, cg.exp_avg, cg.exp_avg_sq = (ctypes.addressof(c) for c in (p, g, m, v))
+                cg.max_exp_avg_sq = None if x is None else ctypes.addressof(x)
+                cg.targets = None if t is None else ctypes.addressof(t)
+                cg.lr, cg.beta1, cg.beta2, cg.eps, cg.tau = lr, b1, b2, eps, self.tau
+            with torch.cuda.device(dev):
+                rc = self._clip_lib.uavx_clip_step(len(calls), self._clip_groups, self._clip_work.data_ptr(),
+                                                   self._clip_work.numel() * 8, self._clip_rec.data_ptr() + 16,
+                                                   self._clip_rec.data_ptr(), st)
+            self._clip.check(rc, "uavx_clip_step")
+            if refresh is not None:
+                refresh.refresh()
+            return
         with torch.cuda.device(dev):
             for gi, tab, (lr, b1, b2, eps), p, g, m, v, x, t in calls:
                 rc = self._lib.uavx_optim_adam(tab.n, p, g, m, v, x, t, tab.numel, lr, b1, b2, eps, self.tau,

@@ -36,7 +36,7 @@ from . import _actor_lib, policy
 from ._fused_common import capture_guard, check_f32, column, rows2, stream
 from .fused_actor import FusedActor
 from .fused_critic import FusedCritic, FusedCriticLoss, FusedTarget
-from .fused_optim import FusedAdam, soft_update
+from .fused_optim import FusedAdam, check_max_grad_norm, soft_update
 from .fused_policy_grad import FusedPolicyGrad
 from .fused_replay import FusedReplaySampler
 from .fused_replay_nstep import N_STEP_MAX, NStepReplaySampler, check_n_step
@@ -46,6 +46,7 @@ from .replay import DeviceReplay
 
 LOG_COLUMNS = _actor_lib.LEARNER_LOG_COLUMNS
 COLUMNS = ("critic_loss_1", "critic_loss_2", "actor_loss", "alpha_loss", "alpha", "actor_updated")
+_CLIP_RECORD = 6         # float32 elements of a FusedAdam clip record: norm, coef, the int64 count, the bound, padding
 
 
 def _cpu(x):
@@ -90,8 +91,9 @@ class _FusedLearner:
     _noises = 0          # [B, 2] standard-normal tensors one update consumes
 
     def _setup(self, device, generator, log_capacity, memory, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6,
-               per_beta=0.0, per_n_step=1):
+               per_beta=0.0, per_n_step=1, max_grad_norm=None):
         self.n_step, self.recency = check_n_step(n_step, recency, type(self).__name__)
+        self.max_grad_norm = self._check_max_grad_norm(max_grad_norm)
         self.prioritized = self.per_eps = None
         if prioritized is not None:
             self.prioritized, self.per_eps = check_prioritized(prioritized, per_eps, type(self).__name__)
@@ -121,10 +123,13 @@ class _FusedLearner:
             raise ValueError(f"uavx: log_capacity must be >= 1, got {log_capacity}")
         self.generator, self.log_capacity = generator, log_capacity
         self._lib = _actor_lib.load()
-        # the loss ring and, behind it in the same allocation, the int64 count the tail launch advances: one copy reads both
-        self._ring = torch.zeros(log_capacity * LOG_COLUMNS + 2, dtype=torch.float32, device=self.device)
-        self._log = self._ring[:-2].view(log_capacity, LOG_COLUMNS)
-        self._updates = self._ring[-2:].view(torch.int64)
+        # the loss ring and, behind it in the same allocation, the int64 count the tail launch advances and the two
+        # optimisers' clip records (critic's, actor's; §26): one copy reads them all
+        n = log_capacity * LOG_COLUMNS
+        self._ring = torch.zeros(n + 2 + 2 * _CLIP_RECORD, dtype=torch.float32, device=self.device)
+        self._log = self._ring[:n].view(log_capacity, LOG_COLUMNS)
+        self._updates = self._ring[n:n + 2].view(torch.int64)
+        self._clip_recs = tuple(self._ring[n + 2 + k * _CLIP_RECORD:n + 2 + (k + 1) * _CLIP_RECORD] for k in range(2))
         self.updates = 0                  # the host's count of updates enqueued: what `updates=None` stands for
         self._losses_in = (ctypes.c_void_p * 3)()
         self._sampler = self._batch = self._y = None
@@ -183,6 +188,50 @@ class _FusedLearner:
         if self._sampler is not None:
             self._sampler.set_beta(beta)
         return self
+
+    # ---- gradient-norm clipping (§26) -----------------------------------------------------------------------------------
+    def _check_max_grad_norm(self, x):
+        """max_grad_norm as (the critic optimiser's bound, the actor optimiser's), each a float or None: a float stands for
+        both, a pair (critic, actor) names them one by one."""
+        what = f"{type(self).__name__}: max_grad_norm"
+        if x is None:
+            return (None, None)
+        if isinstance(x, (tuple, list)):
+            if len(x) != 2:
+                raise ValueError(f"uavx: {what} is a float or a pair (critic, actor), got {len(x)} entries")
+            return tuple(None if v is None else check_max_grad_norm(v, what) for v in x)
+        return (check_max_grad_norm(x, what),) * 2
+
+    def _adams(self):
+        """(the critic's FusedAdam, the actor's)."""
+        raise NotImplementedError
+
+    def _clip_kw(self, k):
+        """FusedAdam's clipping keywords for optimiser k (0 the critic's, 1 the actor's): its record lies behind the loss
+        ring.  Nothing for an unclipped one, which then makes the calls it always made."""
+        bound = self.max_grad_norm[k]
+        return {} if bound is None else dict(max_grad_norm=bound, record=self._clip_recs[k])
+
+    def set_max_grad_norm(self, max_grad_norm):
+        """Moves the clip bounds of a learner built with max_grad_norm (a float for both optimisers, or a pair (critic,
+        actor) in which None leaves that one as it is); the bounds live in device slots, so a captured update follows them.
+        An optimiser built without clipping runs the unclipped step and refuses a bound."""
+        new = self._check_max_grad_norm(max_grad_norm)
+        for adam, bound, name in zip(self._adams(), new, ("critic", "actor")):
+            if bound is not None and adam.max_grad_norm is None:
+                raise ValueError(f"uavx: set_max_grad_norm needs a {type(self).__name__} whose {name} optimiser was built "
+                                 f"with max_grad_norm: this one runs the unclipped step")
+        for adam, bound in zip(self._adams(), new):
+            if bound is not None:
+                adam.set_max_grad_norm(bound)
+        self.max_grad_norm = tuple(a.max_grad_norm for a in self._adams())
+        return self
+
+    def grad_norms(self):
+        """{"critic": (grad_norm, clip_coef, clipped_steps), "actor": (...)} of the optimisers' last steps as 0-d device
+        views (no host synchronisation; reading one does synchronise); None for an optimiser that does not clip."""
+        return {name: None if a.max_grad_norm is None else (a.grad_norm, a.clip_coef, a.clipped_steps)
+                for name, a in zip(("critic", "actor"), self._adams())}
 
     def _q_out(self, rows):
         """The feedback's (q, dq/da) buffers for `rows` rows: reserved ones, or new ones outside a capture.  The weighted
@@ -439,10 +488,25 @@ class _FusedLearner:
     def losses(self, last=None):
         """The last `last` rows of the loss ring (None: all it still holds) in update order, as a numpy [n, 8] array: the
         one host read (a single device-to-host copy of the ring and its count; it synchronises)."""
-        ring = self._ring.cpu()
-        u, log = int(ring[-2:].view(torch.int64)), ring[:-2].view(self.log_capacity, LOG_COLUMNS).numpy()
+        return self._rows(self._ring.cpu(), last)
+
+    def _rows(self, ring, last):
+        size = self.log_capacity * LOG_COLUMNS
+        u, log = int(ring[size:size + 2].view(torch.int64)), ring[:size].view(self.log_capacity, LOG_COLUMNS).numpy()
         n = min(u, self.log_capacity) if last is None else min(int(last), u, self.log_capacity)
         return log[[(u - n + i) % self.log_capacity for i in range(n)]].reshape(n, LOG_COLUMNS)
+
+    def report(self, last=None):
+        """losses(last) and, from the SAME host read, the clip records (§26): (rows, {"critic": (grad_norm, clip_coef,
+        clipped_steps), "actor": (...)}) as Python numbers, None for an optimiser that does not clip."""
+        ring = self._ring.cpu()
+        off = self.log_capacity * LOG_COLUMNS + 2
+        norms = {}
+        for k, name in enumerate(("critic", "actor")):
+            rec = ring[off + k * _CLIP_RECORD:off + (k + 1) * _CLIP_RECORD]
+            norms[name] = None if self.max_grad_norm[k] is None else (float(rec[0]), float(rec[1]),
+                                                                      int(rec[2:4].view(torch.int64)))
+        return self._rows(ring, last), norms
 
     def _set_updates(self, u):
         self.updates = int(u)
@@ -490,13 +554,15 @@ class FusedSAC(_FusedLearner):
 
     def __init__(self, n_states=10, n_actions=2, lr=3e-4, tau=5e-3, gamma=0.99, alpah=2, target_update_interval=1,
                  automatic_entropy_tuning=True, target_entropy=None, device="cuda", generator=None, log_capacity=1024,
-                 memory=None, hidden=256, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1):
+                 memory=None, hidden=256, n_step=1, recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1,
+                 max_grad_norm=None):
         self.lr, self.tau, self.gamma = lr, tau, gamma
         self.target_update_interval = int(target_update_interval)
         if self.target_update_interval < 1:
             raise ValueError(f"uavx: target_update_interval must be >= 1, got {target_update_interval}")
         self.automatic_entropy_tuning = bool(automatic_entropy_tuning)
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step,
+                    max_grad_norm)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden=hidden)
         self.critic = policy.TwinQ(n_states, n_actions, hidden).to(dev)
@@ -525,8 +591,11 @@ class FusedSAC(_FusedLearner):
         self._target = FusedTarget(self._actor_h, self._target_h, gamma=self.gamma)
         self._closs = FusedCriticLoss(self.critic)
         self._pgrad = FusedPolicyGrad(self.policy, self._closs.critic)
-        self._critic_adam = FusedAdam(self.critic_optim, target=self.critic_target, tau=self.tau)
-        self._policy_adam = FusedAdam(self.policy_optim)
+        self._critic_adam = FusedAdam(self.critic_optim, target=self.critic_target, tau=self.tau, **self._clip_kw(0))
+        self._policy_adam = FusedAdam(self.policy_optim, **self._clip_kw(1))
+
+    def _adams(self):
+        return (self._critic_adam, self._policy_adam)
 
     def _handles(self):
         return (self._pgrad, self._closs, self._target, self._actor_h, self._target_h)
@@ -560,7 +629,8 @@ class FusedSAC(_FusedLearner):
 
     def _throwaway(self):
         return FusedSAC(lr=self.lr, tau=self.tau, gamma=self.gamma, device=self.device, log_capacity=1,
-                        automatic_entropy_tuning=self.automatic_entropy_tuning, **self._dims)
+                        automatic_entropy_tuning=self.automatic_entropy_tuning, max_grad_norm=self.max_grad_norm,
+                        **self._dims)
 
     def select_action(self, obs, evaluate=False, out=None, explore=None):
         """sac.py:38-44 over any batch of observations [..., 10] on the device: tanh(mean + std·eps), or tanh(mean) when
@@ -615,8 +685,11 @@ class _ActorCriticLearner(_FusedLearner):
         self._target = FusedTarget(self.actor_target, self.critic_target, gamma=self._gamma, **target_kw)
         self._closs = FusedCriticLoss(self.critic)
         self._pgrad = FusedPolicyGrad(self.actor, self._closs.critic)
-        self._critic_adam = FusedAdam(self.critic_optimizer)
-        self._actor_adam = FusedAdam(self.actor_optimizer, target=self.actor_target, tau=self.tau)
+        self._critic_adam = FusedAdam(self.critic_optimizer, **self._clip_kw(0))
+        self._actor_adam = FusedAdam(self.actor_optimizer, target=self.actor_target, tau=self.tau, **self._clip_kw(1))
+
+    def _adams(self):
+        return (self._critic_adam, self._actor_adam)
 
     def _handles(self):
         return (self._pgrad, self._closs, self._target, self._actor_h)
@@ -671,13 +744,14 @@ class FusedTD3(_ActorCriticLearner):
 
     def __init__(self, state_dim=10, action_dim=2, discount=0.99, tau=0.005, policy_noise=0.2, noise_clip=0.5,
                  policy_freq=2, device="cuda", generator=None, log_capacity=1024, memory=None, hidden=256, n_step=1,
-                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1):
+                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1, max_grad_norm=None):
         self.discount, self.tau, self.policy_noise, self.noise_clip = discount, tau, policy_noise, noise_clip
         self.policy_freq = int(policy_freq)
         if self.policy_freq < 1:
             raise ValueError(f"uavx: policy_freq must be >= 1, got {policy_freq}")
         self.max_action = 1
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step,
+                    max_grad_norm)
         dev = self.device
         self._dims = dict(state_dim=state_dim, action_dim=action_dim, hidden=hidden)
         self.actor = policy.TD3Actor(state_dim, action_dim, hidden).to(dev)
@@ -707,7 +781,7 @@ class FusedTD3(_ActorCriticLearner):
         self._tail(critic_loss, self._actor_and_targets(s) if full else None)
 
     def _throwaway(self):
-        return FusedTD3(device=self.device, log_capacity=1, **self._dims)
+        return FusedTD3(device=self.device, log_capacity=1, max_grad_norm=self.max_grad_norm, **self._dims)
 
     def _explore_defaults(self):
         return {"noise_std": 0.1}
@@ -748,10 +822,11 @@ class FusedDDPG(_ActorCriticLearner):
 
     def __init__(self, n_states=10, n_actions=2, noise_std_dev=0.2, actor_lr=1e-4, critic_lr=1e-3, tau=5e-3, gamma=0.99,
                  device="cuda", generator=None, log_capacity=1024, memory=None, hidden1=400, hidden2=300, n_step=1,
-                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1):
+                 recency=0.0, prioritized=None, per_eps=1e-6, per_beta=0.0, per_n_step=1, max_grad_norm=None):
         self.n_states, self.n_actions = n_states, n_actions
         self.noise_std_dev, self.tau, self.gamma = float(noise_std_dev), tau, gamma
-        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step)
+        self._setup(device, generator, log_capacity, memory, n_step, recency, prioritized, per_eps, per_beta, per_n_step,
+                    max_grad_norm)
         dev = self.device
         self._dims = dict(n_states=n_states, n_actions=n_actions, hidden1=hidden1, hidden2=hidden2)
         self.actor = ddpg_init(policy.DDPGActor(n_states, n_actions, hidden1, hidden2), 5e-4).to(dev)     # model.py:8,19-22
@@ -772,7 +847,7 @@ class FusedDDPG(_ActorCriticLearner):
         self._tail(critic_loss, self._actor_and_targets(s))
 
     def _throwaway(self):
-        return FusedDDPG(device=self.device, log_capacity=1, **self._dims)
+        return FusedDDPG(device=self.device, log_capacity=1, max_grad_norm=self.max_grad_norm, **self._dims)
 
     def _explore_defaults(self):
         return {"ou_sigma": self.noise_std_dev}
