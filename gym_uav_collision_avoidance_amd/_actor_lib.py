@@ -1,5 +1,5 @@
 """ctypes binding of libuavx_actor.so: the fused actor, critic, TD-target, gradient, optimiser, replay, learner-tail and
-exploration kernels.  UNITS describes its ten units once -- header, bound ABI version, every exported function with its
+exploration kernels.  UNITS describes its eleven units once -- header, bound ABI version, every exported function with its
 restype and argtypes -- and load(), _sources() and the *_HEADER, *_SYMBOLS and *_ABI_VERSION names all come from that table.
 Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so that the environment
 library and the source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device
@@ -134,13 +134,19 @@ UNITS = (
         "uavx_nstep_version": (_i32, []),
         "uavx_nstep_workspace_bytes": (_i32, [_i64, _pi64]),
         "uavx_nstep_sample": (_i32, [ctypes.POINTER(NStepArgs), _vp])}),
+    _unit("weighted critic-gradient", "uavx_wcritic_grad.h", 1, {
+        "uavx_wcritic_grad_version": (_i32, []),
+        "uavx_wcritic_grad_workspace_bytes": (_i32, [_i32, _i32, _i32, _i32, _i64, _pi64]),
+        "uavx_wcritic_grad": (_i32, [_i32, _i32, _i32, _i32, _i32, _pvp, _vp, _i64, _i64, _vp, _i64, _vp, _i64, _vp, _i64,
+                                     _pvp, _vp, _vp, _vp, _i64, _vp])}),
 )
 (HEADER, CRITIC_HEADER, GRAD_HEADER, OPTIM_HEADER, REPLAY_HEADER, ACTION_GRAD_HEADER, POLICY_GRAD_HEADER, LEARNER_HEADER,
- EXPLORE_HEADER, NSTEP_HEADER) = (u.header for u in UNITS)
+ EXPLORE_HEADER, NSTEP_HEADER, WGRAD_HEADER) = (u.header for u in UNITS)
 (SYMBOLS, CRITIC_SYMBOLS, GRAD_SYMBOLS, OPTIM_SYMBOLS, REPLAY_SYMBOLS, ACTION_GRAD_SYMBOLS, POLICY_GRAD_SYMBOLS,
- LEARNER_SYMBOLS, EXPLORE_SYMBOLS, NSTEP_SYMBOLS) = (tuple(u.functions) for u in UNITS)
+ LEARNER_SYMBOLS, EXPLORE_SYMBOLS, NSTEP_SYMBOLS, WGRAD_SYMBOLS) = (tuple(u.functions) for u in UNITS)
 (ABI_VERSION, CRITIC_ABI_VERSION, GRAD_ABI_VERSION, OPTIM_ABI_VERSION, REPLAY_ABI_VERSION, ACTION_GRAD_ABI_VERSION,
- POLICY_GRAD_ABI_VERSION, LEARNER_ABI_VERSION, EXPLORE_ABI_VERSION, NSTEP_ABI_VERSION) = (u.abi for u in UNITS)
+ POLICY_GRAD_ABI_VERSION, LEARNER_ABI_VERSION, EXPLORE_ABI_VERSION, NSTEP_ABI_VERSION,
+ WGRAD_ABI_VERSION) = (u.abi for u in UNITS)
 
 
 def _sources():
@@ -149,7 +155,7 @@ def _sources():
 
 
 def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the ten headers of include/, plus
+    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the eleven headers of include/, plus
     the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
     return _native.source_hash(CSRC, _sources())
 
@@ -190,3 +196,12 @@ def check(rc, what):
 def check_critic(rc, what):
     if rc != OK:
         raise RuntimeError(f"uavx: {what} failed: {load().uavx_critic_strerror(rc).decode()} ({rc})")
+
+
+_WGRAD_ERRORS = {ERR_INVALID_ARG: "invalid argument", ERR_HIP: "HIP error", ERR_UNSUPPORTED: "unsupported"}
+
+
+def check_wgrad(rc, what):
+    """uavx_wcritic_grad.h has no strerror of its own, and uavx_critic_strerror words two of its three codes otherwise."""
+    if rc != OK:
+        raise RuntimeError(f"uavx: {what} failed: {_WGRAD_ERRORS.get(rc, 'unknown error')} ({rc})")

@@ -1,5 +1,8 @@
 // Critic-loss gradients (include/uavx_critic_grad.h): the forward with saved activations, the MSE / L1 loss and the
-// backward of the learners' critic update, in three launches.  DESIGN.md §14.
+// backward of the learners' critic update, in three launches.  DESIGN.md §14.  The weighted call
+// (include/uavx_wcritic_grad.h) is the same three launches: a per-row importance-sampling weight enters dq
+// and the loss term once, in the row pass's 16-thread dq step, and q(s, a) is an output; every summation order is shared,
+// so a weight of 1 gives the unweighted gradients and losses bit for bit.
 //
 // The lane layout of the MFMA products, layer 1, the W1 / b1 tail, the small helpers and the weights launch are shared with
 // the other gradient units: uavx_grad_impl.hpp.
@@ -8,7 +11,8 @@
 //                    Layer 1 (f64, rounded once) into LDS and to the workspace, for dW2; z2ᵀ = W2·h1ᵀ with wave w
 //                    taking the 16-unit blocks j ≡ w (mod 4), each 16-wide k block's MFMA chain added up in f64, z2
 //                    written to the workspace; q summed over units and waves in a fixed order;
-//                    dq per row; then per unit block again: δ2 = dq·w3 ⊙ act′(z2) over z2 in the workspace, and
+//                    dq per row (W: times the row's weight, and q written out);
+//                    then per unit block again: δ2 = dq·w3 ⊙ act′(z2) over z2 in the workspace, and
 //                    δ1ᵀ += W2ᵀ·δ2ᵀ straight from the δ2 accumulator (its k order is the unit order of the block).  The
 //                    four waves' δ1 are summed through LDS in wave order.  The block's sums over its 16 rows of the
 //                    small gradients (W1, b1, b2, W3, b3) and of the loss go to a per-block partial row (f64).
@@ -18,6 +22,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uavx_critic_grad.h"
+#include "../../include/uavx_wcritic_grad.h"
 #include "uavx_grad_impl.hpp"
 
 namespace uavx_critic_grad_k {
@@ -52,9 +57,14 @@ struct RowArgs {
     int h1, h2, nb2, lp, loss;
     double mse_scale;                  // 2.0 / rows
     float dq_scale;                    // L1: 1.f / rows
+    // read by the weighted instantiations alone, and last, so that every member above keeps its offset
+    const float *weight;               // nullptr: every weight is 1
+    float *q_out;                      // [towers][rows], or nullptr
+    int64_t w_stride;
 };
 
-template <bool LEAKY, int NB1>
+// W: the weighted call.  The dq step is the only place the two forms differ.
+template <bool LEAKY, int NB1, bool W>
 __global__ __launch_bounds__(WG) void grad_rows(RowArgs a) {
     constexpr int N1 = 16 * NB1, HP = N1 + 4;
     __shared__ float xs[16][IN];
@@ -137,16 +147,34 @@ __global__ __launch_bounds__(WG) void grad_rows(RowArgs a) {
         for (int w = 1; w < WAVES; ++w) q += qs[w][tid];
         q += (double)b3[0];
         float dq = 0.f, l = 0.f;
-        if (row < a.rows) {
-            const double dd = q - (double)a.y[row * a.y_stride];
-            const float d = (float)dd;
-            if (a.loss == UAVX_CRITIC_GRAD_MSE) {
-                dq = (float)(dd * a.mse_scale);   // mse_loss_backward: (q − y) · (2 / B), rounded once
-                l = (float)(dd * dd);
-            } else {
-                const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);   // torch.sign (0 for 0 and NaN)
-                dq = sg * a.dq_scale;         // mean then abs backward: sign(q − y) · (1 / B)
-                l = fabsf(d);
+        if constexpr (W) {
+            if (row < a.rows) {
+                // the weight enters here, once: dq and the loss term are linear in it, everything downstream is in dq
+                const float w = a.weight ? a.weight[row * a.w_stride] : 1.f;
+                const double dd = q - (double)a.y[row * a.y_stride];
+                const float d = (float)dd;
+                if (a.loss == UAVX_WCRITIC_MSE) {
+                    dq = (float)(((double)w * dd) * a.mse_scale);   // w · (q − y) · (2 / B), rounded once
+                    l = (float)((double)w * dd * dd);
+                } else {
+                    const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);   // torch.sign (0 for 0 and NaN)
+                    dq = sg * (w * a.dq_scale);   // w · sign(q − y) · (1 / B)
+                    l = w * fabsf(d);
+                }
+                if (a.q_out) a.q_out[t * a.rows + row] = (float)q;
+            }
+        } else {
+            if (row < a.rows) {
+                const double dd = q - (double)a.y[row * a.y_stride];
+                const float d = (float)dd;
+                if (a.loss == UAVX_CRITIC_GRAD_MSE) {
+                    dq = (float)(dd * a.mse_scale);   // mse_loss_backward: (q − y) · (2 / B), rounded once
+                    l = (float)(dd * dd);
+                } else {
+                    const float sg = d > 0.f ? 1.f : (d < 0.f ? -1.f : 0.f);   // torch.sign (0 for 0 and NaN)
+                    dq = sg * a.dq_scale;         // mean then abs backward: sign(q − y) · (1 / B)
+                    l = fabsf(d);
+                }
             }
         }
         dqs[tid] = dq;
@@ -259,14 +287,13 @@ struct Plan {
     int64_t b16, kc, h1_tower, d2_tower, p_tower, off_d2, off_p, off_part2, off_partp, bytes;
 };
 
-Plan plan(const uavx_critic *h, int64_t rows) {
+Plan plan(int nb1, int h1, int h2, int T, int64_t rows) {
     Plan p;
-    const int T = h->towers;
-    p.n1 = 16 * h->L.nb1;
-    p.nb2 = (h->h2 + 15) / 16;
-    p.lp = (small_layout(h->h1, h->h2).n + 3) & ~3;
-    p.tj = (h->h2 + 63) / 64;
-    p.ti = (h->h1 + 63) / 64;
+    p.n1 = 16 * nb1;
+    p.nb2 = (h2 + 15) / 16;
+    p.lp = (small_layout(h1, h2).n + 3) & ~3;
+    p.tj = (h2 + 63) / 64;
+    p.ti = (h1 + 63) / 64;
     p.pchunks = (p.lp + 255) / 256;
     p.b16 = (rows + 15) / 16 * 16;
     split_k((int64_t)T * p.tj * p.ti, p.b16, &p.kc, &p.S);
@@ -276,7 +303,7 @@ Plan plan(const uavx_critic *h, int64_t rows) {
     p.off_d2 = align256(T * p.h1_tower * 4);
     p.off_p = p.off_d2 + align256(T * p.d2_tower * 4);
     p.off_part2 = p.off_p + align256(T * p.p_tower * 8);
-    p.off_partp = p.off_part2 + align256((int64_t)p.S * T * h->h2 * h->h1 * 4);
+    p.off_partp = p.off_part2 + align256((int64_t)p.S * T * h2 * h1 * 4);
     p.bytes = p.off_partp + align256((int64_t)p.S * T * p.lp * 8);
     return p;
 }
@@ -290,34 +317,33 @@ int check_handle(const uavx_critic *h, int64_t rows) {
     return UAVX_CRITIC_OK;
 }
 
-}  // namespace
+constexpr int MAX_H2 = 1 << 20;    // keeps every int offset of a partial row (13·h1 + 2·h2 + 2) far from overflow
 
-extern "C" {
-
-int uavx_critic_grad_version(void) { return UAVX_CRITIC_GRAD_VERSION; }
-
-int uavx_critic_grad_workspace_bytes(const uavx_critic *h, int64_t rows, int64_t *bytes) {
-    if (!bytes) return UAVX_CRITIC_ERR_INVALID_ARG;
-    *bytes = 0;
-    const int rc = check_handle(h, rows);
-    if (rc != UAVX_CRITIC_OK) return rc;
-    *bytes = plan(h, rows).bytes;
-    return UAVX_CRITIC_OK;
+// the weighted call takes no handle: check_handle's limits (the tiles uavx_critic_create accepts) on the dimensions
+// themselves -> nb1 through *nb1
+int check_dims(int kind, int h1, int h2, int towers, int64_t rows, int *nb1) {
+    if (kind != UAVX_WCRITIC_SAC && kind != UAVX_WCRITIC_TD3 && kind != UAVX_WCRITIC_DDPG) return UAVX_WCRITIC_ERR_INVALID_ARG;
+    if (rows < 1 || rows > UAVX_WCRITIC_GRAD_MAX_ROWS || towers < 1 || towers > 2 || h2 < 1 || h2 > MAX_H2)
+        return UAVX_WCRITIC_ERR_INVALID_ARG;
+    *nb1 = kind == UAVX_WCRITIC_DDPG ? 25 : 16;
+    if (h1 <= 16 * (*nb1 - 1) || h1 > 16 * *nb1) return UAVX_WCRITIC_ERR_UNSUPPORTED;
+    return UAVX_WCRITIC_OK;
 }
 
-int uavx_critic_grad(const uavx_critic *h, int loss, const float *const *params, const float *state, int64_t rows,
-                     int64_t s_stride, const float *action, int64_t a_stride, const float *y, int64_t y_stride,
-                     float *const *grads, float *loss_out, void *workspace, int64_t workspace_bytes, void *stream) {
-    if (!h || !params || !grads || rows < 1 || s_stride < OBS || a_stride < 2 || y_stride < 1)
-        return UAVX_CRITIC_ERR_INVALID_ARG;
-    if (loss != UAVX_CRITIC_GRAD_MSE && loss != UAVX_CRITIC_GRAD_L1) return UAVX_CRITIC_ERR_INVALID_ARG;
-    if (!state || !action || !y || !loss_out || !workspace || ((uintptr_t)workspace & 15)) return UAVX_CRITIC_ERR_INVALID_ARG;
-    const int rc = check_handle(h, rows);
-    if (rc != UAVX_CRITIC_OK) return rc;
-    const int T = h->towers;
+// the two headers' status codes are uavx_critic.h's values, so launch() serves both entry points
+static_assert(UAVX_WCRITIC_OK == UAVX_CRITIC_OK && UAVX_WCRITIC_ERR_INVALID_ARG == UAVX_CRITIC_ERR_INVALID_ARG &&
+              UAVX_WCRITIC_ERR_HIP == UAVX_CRITIC_ERR_HIP && UAVX_WCRITIC_ERR_UNSUPPORTED == UAVX_CRITIC_ERR_UNSUPPORTED, "");
+static_assert((int)UAVX_WCRITIC_MSE == (int)UAVX_CRITIC_GRAD_MSE && (int)UAVX_WCRITIC_L1 == (int)UAVX_CRITIC_GRAD_L1, "");
+
+// The three launches of both entry points, behind their argument checks.  weighted: the W instantiation of the row pass
+// (weight and q_out may each be NULL there); nb1: 25 for the leaky (DDPG) tile, 16 for the relu one.
+int launch(bool weighted, int nb1, int h1, int h2, int T, int loss, const float *const *params, const float *state,
+           int64_t rows, int64_t s_stride, const float *action, int64_t a_stride, const float *y, int64_t y_stride,
+           const float *weight, int64_t w_stride, float *const *grads, float *loss_out, float *q_out, void *workspace,
+           int64_t workspace_bytes, void *stream) {
     for (int i = 0; i < 6 * T; ++i)
         if (!params[i] || !grads[i]) return UAVX_CRITIC_ERR_INVALID_ARG;
-    const Plan p = plan(h, rows);
+    const Plan p = plan(nb1, h1, h2, T, rows);
     if (workspace_bytes < p.bytes) return UAVX_CRITIC_ERR_INVALID_ARG;
     char *ws = (char *)workspace;
     const hipStream_t st = (hipStream_t)stream;
@@ -344,14 +370,18 @@ int uavx_critic_grad(const uavx_critic *h, int loss, const float *const *params,
     ra.h1_tower = p.h1_tower;
     ra.d2_tower = p.d2_tower;
     ra.p_tower = p.p_tower;
-    ra.h1 = h->h1;
-    ra.h2 = h->h2;
+    ra.h1 = h1;
+    ra.h2 = h2;
     ra.nb2 = p.nb2;
     ra.lp = p.lp;
     ra.loss = loss;
     ra.mse_scale = 2.0 / (double)rows;
     ra.dq_scale = 1.f / (float)rows;
-    const rows_fn fr = h->kind == UAVX_CRITIC_DDPG ? grad_rows<true, 25> : grad_rows<false, 16>;
+    ra.weight = weight;
+    ra.q_out = q_out;
+    ra.w_stride = weight ? w_stride : 0;
+    const rows_fn fr = nb1 == 25 ? (weighted ? grad_rows<true, 25, true> : grad_rows<true, 25, false>)
+                                 : (weighted ? grad_rows<false, 16, true> : grad_rows<false, 16, false>);
     hipLaunchKernelGGL(fr, dim3((unsigned)(p.b16 / 16), (unsigned)T), dim3(WG), 0, st, ra);
     if (hipGetLastError() != hipSuccess) return UAVX_CRITIC_ERR_HIP;
 
@@ -366,9 +396,9 @@ int uavx_critic_grad(const uavx_critic *h, int loss, const float *const *params,
     wa.partp = (double *)(ws + p.off_partp);
     wa.b16 = p.b16;
     wa.kc = p.kc;
-    wa.h1 = h->h1;
+    wa.h1 = h1;
     wa.n1 = p.n1;
-    wa.h2 = h->h2;
+    wa.h2 = h2;
     wa.nb2 = p.nb2;
     wa.lp = p.lp;
     wa.towers = T;
@@ -384,14 +414,69 @@ int uavx_critic_grad(const uavx_critic *h, int loss, const float *const *params,
     for (int i = 0; i < 6 * T; ++i) ca.grads[i] = grads[i];
     ca.loss = loss_out;
     ca.rows = rows;
-    ca.h1 = h->h1;
-    ca.h2 = h->h2;
+    ca.h1 = h1;
+    ca.h2 = h2;
     ca.lp = p.lp;
     ca.towers = T;
     ca.S = p.S;
-    const int64_t n = (int64_t)T * ((int64_t)h->h2 * h->h1 + small_layout(h->h1, h->h2).n);
+    const int64_t n = (int64_t)T * ((int64_t)h2 * h1 + small_layout(h1, h2).n);
     hipLaunchKernelGGL(grad_combine, dim3((unsigned)((n + WG - 1) / WG)), dim3(WG), 0, st, ca);
     return hipGetLastError() == hipSuccess ? UAVX_CRITIC_OK : UAVX_CRITIC_ERR_HIP;
+}
+
+}  // namespace
+
+extern "C" {
+
+int uavx_critic_grad_version(void) { return UAVX_CRITIC_GRAD_VERSION; }
+
+int uavx_critic_grad_workspace_bytes(const uavx_critic *h, int64_t rows, int64_t *bytes) {
+    if (!bytes) return UAVX_CRITIC_ERR_INVALID_ARG;
+    *bytes = 0;
+    const int rc = check_handle(h, rows);
+    if (rc != UAVX_CRITIC_OK) return rc;
+    *bytes = plan(h->L.nb1, h->h1, h->h2, h->towers, rows).bytes;
+    return UAVX_CRITIC_OK;
+}
+
+int uavx_critic_grad(const uavx_critic *h, int loss, const float *const *params, const float *state, int64_t rows,
+                     int64_t s_stride, const float *action, int64_t a_stride, const float *y, int64_t y_stride,
+                     float *const *grads, float *loss_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!h || !params || !grads || rows < 1 || s_stride < OBS || a_stride < 2 || y_stride < 1)
+        return UAVX_CRITIC_ERR_INVALID_ARG;
+    if (loss != UAVX_CRITIC_GRAD_MSE && loss != UAVX_CRITIC_GRAD_L1) return UAVX_CRITIC_ERR_INVALID_ARG;
+    if (!state || !action || !y || !loss_out || !workspace || ((uintptr_t)workspace & 15)) return UAVX_CRITIC_ERR_INVALID_ARG;
+    const int rc = check_handle(h, rows);
+    if (rc != UAVX_CRITIC_OK) return rc;
+    return launch(false, h->L.nb1, h->h1, h->h2, h->towers, loss, params, state, rows, s_stride, action, a_stride, y, y_stride,
+                  nullptr, 0, grads, loss_out, nullptr, workspace, workspace_bytes, stream);
+}
+
+int uavx_wcritic_grad_version(void) { return UAVX_WCRITIC_GRAD_VERSION; }
+
+int uavx_wcritic_grad_workspace_bytes(int kind, int h1, int h2, int towers, int64_t rows, int64_t *bytes) {
+    if (!bytes) return UAVX_WCRITIC_ERR_INVALID_ARG;
+    *bytes = 0;
+    int nb1 = 0;
+    const int rc = check_dims(kind, h1, h2, towers, rows, &nb1);
+    if (rc != UAVX_WCRITIC_OK) return rc;
+    *bytes = plan(nb1, h1, h2, towers, rows).bytes;
+    return UAVX_WCRITIC_OK;
+}
+
+int uavx_wcritic_grad(int kind, int h1, int h2, int towers, int loss, const float *const *params, const float *state,
+                      int64_t rows, int64_t s_stride, const float *action, int64_t a_stride, const float *y,
+                      int64_t y_stride, const float *weight, int64_t w_stride, float *const *grads, float *loss_out,
+                      float *q_out, void *workspace, int64_t workspace_bytes, void *stream) {
+    if (!params || !grads || rows < 1 || s_stride < OBS || a_stride < 2 || y_stride < 1) return UAVX_WCRITIC_ERR_INVALID_ARG;
+    if (weight && w_stride < 1) return UAVX_WCRITIC_ERR_INVALID_ARG;
+    if (loss != UAVX_WCRITIC_MSE && loss != UAVX_WCRITIC_L1) return UAVX_WCRITIC_ERR_INVALID_ARG;
+    if (!state || !action || !y || !loss_out || !workspace || ((uintptr_t)workspace & 15)) return UAVX_WCRITIC_ERR_INVALID_ARG;
+    int nb1 = 0;
+    const int rc = check_dims(kind, h1, h2, towers, rows, &nb1);
+    if (rc != UAVX_WCRITIC_OK) return rc;
+    return launch(true, nb1, h1, h2, towers, loss, params, state, rows, s_stride, action, a_stride, y, y_stride, weight,
+                  w_stride, grads, loss_out, q_out, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

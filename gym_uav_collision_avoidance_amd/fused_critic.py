@@ -21,7 +21,7 @@ import ctypes
 
 import torch
 
-from . import _actor_lib, _wgrad_lib
+from . import _actor_lib
 from ._fused_common import (KIND_NAMES, PRECISIONS, ParamSlots, Workspace, actor_layers, alpha_arg, check_buffers,
                             check_on_gpu, check_packable, column, critic_layers, noise_arg, pack_pointers, rows2,
                             stream)
@@ -238,7 +238,6 @@ class FusedCriticLoss:
         self._slots = ParamSlots((p for lin in fc._layers for p in (lin.weight, lin.bias)), 12, "FusedCriticLoss", "critic")
         self._loss = torch.zeros(fc.towers, dtype=torch.float32, device=self.device)
         self._ws = Workspace(self.device)
-        self._wlib = None
 
     def workspace_bytes(self, rows):
         n = ctypes.c_int64()
@@ -248,18 +247,9 @@ class FusedCriticLoss:
 
     def reserve(self, rows):
         """Grows the workspace to what `rows` rows need (a graph capture cannot allocate it).  One workspace serves the
-        unweighted and the weighted call: for the same critic and rows the two libraries ask for the same layout."""
+        unweighted and the weighted call: both lay it out by one plan."""
         self._ws.reserve(self.workspace_bytes(rows))
         return self
-
-    def _weighted(self):
-        """libuavx_wgrad.so, loaded by the first call that passes a weight or asks for q."""
-        if self._wlib is None:
-            if self.critic.precision != "f32":
-                raise RuntimeError(f"uavx: the weighted critic gradient has no kernel compiled for a "
-                                   f"{self.critic.precision} FusedCritic (f32 only)")
-            self._wlib = _wgrad_lib.load()
-        return self._wlib
 
     def backward(self, state, action, y, weight=None, q_out=None):
         """Overwrites every critic parameter's .grad with the gradient of the loss on [B, 10] states, [B, 2] actions
@@ -269,9 +259,9 @@ class FusedCriticLoss:
         weight: per-row importance-sampling weights w ([B] or [B, 1] float32, any positive stride; finite and >= 0, which
         is not checked on the device): the loss becomes mean_b w_b (q - y)^2, or mean_b w_b |q - y|.  q_out: a contiguous
         [towers, B] float32 tensor that receives q(s, a) of the live critic, what a prioritized sampler's
-        update_priorities takes.  With either given the call goes to libuavx_wgrad.so (include/uavx_wcritic_grad.h, three
-        launches as well); weight=None there stands for a weight of 1, which gives the unweighted gradients bit for bit.
-        With both None the call is the unweighted one of libuavx_actor.so."""
+        update_priorities takes.  With either given the call is uavx_wcritic_grad (include/uavx_wcritic_grad.h, the same
+        three launches with the weighted row pass); weight=None there stands for a weight of 1, which gives the unweighted
+        gradients bit for bit.  With both None the call is uavx_critic_grad."""
         dev = self.device
         rows, s_stride = rows2(state, self.critic.obs_dim, dev, "state")
         arows, a_stride = rows2(action, self.critic.act_dim, dev, "action")
@@ -290,7 +280,9 @@ class FusedCriticLoss:
         if q_out is not None:
             check_buffers(((q_out, (self.critic.towers, rows), "q_out"),), dev)
             q_ptr = q_out.data_ptr()
-        wlib = self._weighted() if weighted else None
+        if weighted and self.critic.precision != "f32":
+            raise RuntimeError(f"uavx: the weighted critic gradient has no kernel compiled for a "
+                               f"{self.critic.precision} FusedCritic (f32 only)")
         pptrs = self._slots.fill_params(dev)
         self._ws.ensure(self.workspace_bytes(rows), rows)
         ws = self._ws.buf
@@ -302,11 +294,11 @@ class FusedCriticLoss:
         else:
             fc = self.critic
             with torch.cuda.device(dev):
-                rc = wlib.uavx_wcritic_grad(self.kind, fc.hidden1, fc.hidden2, fc.towers, _LOSSES[self.loss], pptrs,
-                                            state.data_ptr(), rows, s_stride, action.data_ptr(), a_stride, y.data_ptr(),
-                                            y_stride, w_ptr, w_stride, self._slots.fill_grads(), self._loss.data_ptr(),
-                                            q_ptr, ws.data_ptr(), ws.numel(), stream(dev))
-            _wgrad_lib.check(rc, "uavx_wcritic_grad")
+                rc = self._lib.uavx_wcritic_grad(self.kind, fc.hidden1, fc.hidden2, fc.towers, _LOSSES[self.loss], pptrs,
+                                                 state.data_ptr(), rows, s_stride, action.data_ptr(), a_stride,
+                                                 y.data_ptr(), y_stride, w_ptr, w_stride, self._slots.fill_grads(),
+                                                 self._loss.data_ptr(), q_ptr, ws.data_ptr(), ws.numel(), stream(dev))
+            _actor_lib.check_wgrad(rc, "uavx_wcritic_grad")
         return (self._loss[0], self._loss[1]) if self.critic.towers == 2 else self._loss[0]
 
     def close(self):

@@ -1,4 +1,4 @@
-/* uavx_wcritic_grad.h — C ABI of the WEIGHTED critic-loss gradient in libuavx_wgrad.so: the critic-loss gradient of
+/* uavx_wcritic_grad.h — C ABI of the WEIGHTED critic-loss gradient in libuavx_actor.so: the critic-loss gradient of
  * include/uavx_critic_grad.h with a per-row importance-sampling weight (prioritized replay, beta > 0) and the live
  * critic's q(s, a) as an output, on MI355X (gfx950), f32.  DESIGN.md §24.
  *
@@ -11,7 +11,7 @@
  * and loss equals uavx_critic_grad's bit for bit: the summation orders are the same.  A row of weight 0 contributes exact
  * zeros, like a padded row.  Weights are not validated on the device (a NaN propagates): the caller keeps them finite, >= 0.
  *
- * The library stands beside libuavx_actor.so and takes no uavx_critic handle: kind, h1, h2 and towers are arguments.
+ * The call takes no uavx_critic handle: kind, h1, h2 and towers are arguments.
  *
  * Conventions (as uavx_critic_grad.h)
  *   - buffer arguments are DEVICE pointers on the current device; work is enqueued on `stream` (hipStream_t as void*,

@@ -130,7 +130,7 @@ def test_action_grad_kernels_no_spills_no_scratch():
     assert set(rec) == set(names)
     # the existing tiles keep their counts: nothing of the new unit is named like them
     assert sum(r["name"].startswith("uavx_critic_k::critic_fwd<") for r in rows) == 16
-    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 3
+    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 5      # grad_combine, and each tile of grad_rows unweighted and weighted
 
 
 def test_python_action_grad_api_rejects_bad_modules_before_the_device():

@@ -82,8 +82,10 @@ def test_grad_kernels_no_spills_no_scratch():
     rows = _kernels()
     grad = [r for r in rows if r["name"].startswith("uavx_critic_grad_k::")]
     names = sorted(r["name"] for r in grad)
-    assert names == ["uavx_critic_grad_k::grad_combine", "uavx_critic_grad_k::grad_rows<false, 16>",
-                     "uavx_critic_grad_k::grad_rows<true, 25>"], names
+    # each tile of the row pass twice: the unweighted call's and the weighted one's (include/uavx_wcritic_grad.h)
+    assert names == ["uavx_critic_grad_k::grad_combine", "uavx_critic_grad_k::grad_rows<false, 16, false>",
+                     "uavx_critic_grad_k::grad_rows<false, 16, true>", "uavx_critic_grad_k::grad_rows<true, 25, false>",
+                     "uavx_critic_grad_k::grad_rows<true, 25, true>"], names
     # the dW2 weights kernel this unit shares with the actor backward (actor_csrc/uavx_grad_common.hip)
     shared = [r for r in rows if r["name"].startswith("uavx_grad_k::")]
     assert [r["name"] for r in shared] == ["uavx_grad_k::grad_weights"], shared

@@ -1,6 +1,7 @@
 """Host-side checks of the learner bindings' shared layer: _actor_lib's table of units gives the
 sources and every public constant the hand-written module gave (values recorded at commit 1ba5a5c; the tenth unit, the
-n-step sampler, and the per-file hashes at 9a32f7c), covers every exported symbol, and every class built on the kind
+n-step sampler, and the per-file hashes at 9a32f7c; the eleventh unit, the weighted critic gradient, at the commit that
+folded it into uavx_critic_grad.hip), covers every exported symbol, and every class built on the kind
 tables and on critic_handle refuses a wrong class, a wrong pair and a CPU module with the message it had there -- before
 the library is loaded, so without a GPU."""
 import hashlib
@@ -14,17 +15,21 @@ import torch
 from gym_uav_collision_avoidance_amd import _actor_lib, _native, policy
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-# source_hash() at the commit that moved the n-step sampler into uavx_replay.hip (ab517ee91bb05350 before it)
-MERGED_HASH = "a056e385b4f6651e"
+# source_hash() at the commit that folded the weighted critic gradient into uavx_critic_grad.hip, the second commit that moved
+# it on purpose (a056e385b4f6651e before it, from the commit that moved the n-step sampler into uavx_replay.hip;
+# ab517ee91bb05350 before that)
+MERGED_HASH = "17c0e2c29cadcdb4"
 PARENT_SOURCES = [
     "uavx_action_grad.hip", "uavx_actor.hip", "uavx_actor_impl.hpp", "uavx_critic.hip", "uavx_critic_grad.hip",
     "uavx_explore.hip", "uavx_grad_common.hip", "uavx_grad_impl.hpp", "uavx_learner.hip", "uavx_optim.hip",
     "uavx_policy_grad.hip", "uavx_replay.hip", "uavx_actor.h", "uavx_critic.h", "uavx_critic_grad.h", "uavx_optim.h",
-    "uavx_replay.h", "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h", "uavx_nstep.h"]
+    "uavx_replay.h", "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h", "uavx_nstep.h",
+    "uavx_wcritic_grad.h"]
 UNIT_NAMES = ("", "CRITIC_", "GRAD_", "OPTIM_", "REPLAY_", "ACTION_GRAD_", "POLICY_GRAD_", "LEARNER_", "EXPLORE_",
-              "NSTEP_")
+              "NSTEP_", "WGRAD_")
 PARENT_HEADERS = ("uavx_actor.h", "uavx_critic.h", "uavx_critic_grad.h", "uavx_optim.h", "uavx_replay.h",
-                  "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h", "uavx_nstep.h")
+                  "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h", "uavx_nstep.h",
+                  "uavx_wcritic_grad.h")
 PARENT_SYMBOLS = (
     ("uavx_actor_version", "uavx_actor_strerror", "uavx_actor_create", "uavx_actor_destroy", "uavx_actor_pack",
      "uavx_actor_forward"),
@@ -38,7 +43,8 @@ PARENT_SYMBOLS = (
      "uavx_policy_grad_backward"),
     ("uavx_learner_version", "uavx_learner_tail"),
     ("uavx_explore_version", "uavx_explore_act"),
-    ("uavx_nstep_version", "uavx_nstep_workspace_bytes", "uavx_nstep_sample"))
+    ("uavx_nstep_version", "uavx_nstep_workspace_bytes", "uavx_nstep_sample"),
+    ("uavx_wcritic_grad_version", "uavx_wcritic_grad_workspace_bytes", "uavx_wcritic_grad"))
 PARENT_CONSTANTS = dict(
     SAC=0, TD3=1, DDPG=2, F32=0, BF16=1, RAW=0, DETERMINISTIC=1, SAC_SAMPLE=2, ADD_CLAMP=3, OK=0, ERR_INVALID_ARG=-1,
     ERR_HIP=-2, ERR_UNSUPPORTED=-3, ERR_NOT_PACKED=-4, SPLIT_ROWS=16384, GRAD_MSE=0, GRAD_L1=1, GRAD_MAX_ROWS=262144,
@@ -46,21 +52,25 @@ PARENT_CONSTANTS = dict(
     POLICY_GRAD_MAX_ROWS=262144, LEARNER_LOG_COLUMNS=8, EXPLORE_MAX_ROWS=16777216, EXPLORE_STATE_BYTES=16, NSTEP_MAX=8,
     NSTEP_MAX_ROWS=1048576, NSTEP_SINGLE_ROWS=1024)
 WORDS = ("actor", "critic", "critic-gradient", "optimiser", "replay", "action-gradient", "policy-gradient", "learner",
-         "exploration", "n-step replay")
+         "exploration", "n-step replay", "weighted critic-gradient")
 
 
 def test_hash_and_sources_are_the_parents():
-    """Nothing outside the replay unit moved: every source but uavx_replay.hip has the code it had at 9a32f7c
-    (golden/actor_sources_parent.json, written there by golden/make_actor_sources.py), and the only file the library
-    gained is the n-step header."""
+    """Nothing outside the replay unit and the critic-gradient unit moved: every source but uavx_replay.hip and
+    uavx_critic_grad.hip has the code it had at 9a32f7c (golden/actor_sources_parent.json, written there by
+    golden/make_actor_sources.py), and the only files the library gained are the n-step header and the weighted
+    critic gradient's.  The hash moved twice, each time for one unit: when the n-step sampler joined uavx_replay.hip, and
+    when the weighted critic gradient, until then a restatement of grad_rows in a library of its own, became a template
+    switch of grad_rows."""
     sources = _actor_lib._sources()
     assert [os.path.basename(p) for p in sources] == PARENT_SOURCES
     assert all(os.path.isfile(p) for p in sources)
     parent = json.load(open(os.path.join(ROOT, "tests", "golden", "actor_sources_parent.json")))
-    assert set(PARENT_SOURCES) == set(parent) | {"uavx_nstep.h"} and "uavx_nstep.h" not in parent
+    gained = {"uavx_nstep.h", "uavx_wcritic_grad.h"}
+    assert set(PARENT_SOURCES) == set(parent) | gained and not gained & set(parent)
     for p in sources:
         name = os.path.basename(p)
-        if name not in ("uavx_replay.hip", "uavx_nstep.h"):
+        if name not in ("uavx_replay.hip", "uavx_critic_grad.hip") and name not in gained:
             code = _native.code_only(open(p, encoding="utf-8").read())
             assert hashlib.sha256(code.encode()).hexdigest() == parent[name], name
     assert _actor_lib.source_hash() == MERGED_HASH

@@ -1,4 +1,4 @@
-"""FusedCriticLoss.backward(weight=, q_out=) (libuavx_wgrad.so, include/uavx_wcritic_grad.h) on the MI355X: a
+"""FusedCriticLoss.backward(weight=, q_out=) (libuavx_actor.so, include/uavx_wcritic_grad.h) on the MI355X: a
 weight of 1 is the unweighted call bit for bit, the weight enters once and linearly, a zero-weight row is a padded row,
 random weights against float64 autograd of the weighted loss (tests/wgrad_ref.py) within §14's bounds, graph capture, and
 the learners' `per_beta` keyword: the sampler's weights reach the critic loss, the gradient's q reaches the priorities,

@@ -1,6 +1,6 @@
 """Host-side checks of the n-step replay sampler (libuavx_actor.so, include/uavx_nstep.h): the library builds for gfx950
 without a GPU and carries its source hash, exports exactly what its header declares, refuses every bad argument before
-touching a device, its kernels use no scratch and spill nothing, it is one unit of ten beside the one-step interface it
+touching a device, its kernels use no scratch and spill nothing, it is one unit of eleven beside the one-step interface it
 shares its kernels with, and the numpy restatement the GPU tests trust (nstep_ref.py) equals a per-row loop written from
 the header's prose, equals replay_ref.sample for one step, and draws step indices with a cumulative distribution of exactly (m/span)^2."""
 import ctypes
@@ -54,7 +54,8 @@ def test_library_exports_exactly_what_the_header_declares():
     hdr = open(x.NSTEP_HEADER).read()
     declared = set(re.findall(r"\b(uavx_nstep_[a-z_0-9]*)\s*\(", hdr))
     assert declared == set(x.NSTEP_SYMBOLS) == {"uavx_nstep_version", "uavx_nstep_workspace_bytes", "uavx_nstep_sample"}
-    assert x.NSTEP_SYMBOLS[0] == x.UNITS[-1].version == "uavx_nstep_version" and x.UNITS[-1].word == "n-step replay"
+    unit, = [u for u in x.UNITS if u.word == "n-step replay"]
+    assert x.NSTEP_SYMBOLS[0] == unit.version == "uavx_nstep_version" and tuple(unit.functions) == x.NSTEP_SYMBOLS
     lib = x.load()
     for name in sorted(declared):
         assert hasattr(lib, name), name
@@ -72,7 +73,7 @@ def test_library_exports_exactly_what_the_header_declares():
 
 def test_one_library_serves_both_sampler_interfaces():
     x = _xlib()
-    assert len(x.UNITS) == 10
+    assert len(x.UNITS) == 11
     pkg = os.path.join(ROOT, "gym_uav_collision_avoidance_amd")
     assert not os.path.exists(os.path.join(pkg, "replay_csrc"))
     assert importlib.util.find_spec("gym_uav_collision_avoidance_amd._replayx_lib") is None

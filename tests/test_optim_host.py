@@ -106,7 +106,7 @@ def test_optim_kernels_no_spills_no_scratch_no_lds():
         assert r["group_segment_fixed_size"] == 0, r
         assert r["agpr_count"] == 0 and r["vgpr_count"] <= 64, r         # 8 waves per SIMD
     # nothing of the new unit is counted among the pinned namespaces
-    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 3
+    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 5      # grad_combine, and each tile of grad_rows unweighted and weighted
 
 
 def test_optim_source_has_no_scalar_memory_writes():

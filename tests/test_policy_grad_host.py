@@ -172,7 +172,7 @@ def test_policy_grad_kernels_no_spills_no_scratch():
             assert rec[r["name"]][f] == r[f], (r["name"], f, rec[r["name"]][f], r[f])
     # the existing tiles keep their counts: nothing of the new unit is named like them, nothing of theirs changed
     assert sum(r["name"].startswith("uavx_critic_k::critic_fwd<") for r in rows) == 16
-    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 3
+    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 5      # grad_combine, and each tile of grad_rows unweighted and weighted
     assert sum(r["name"].startswith("uavx_action_grad_k::") for r in rows) == 2
     assert sum(r["name"].startswith("uavx_optim_k::") for r in rows) == 3
 

@@ -133,7 +133,7 @@ def test_replay_kernels_within_budget():
         assert r["group_segment_fixed_size"] <= 8192, r
         assert r["agpr_count"] == 0 and r["vgpr_count"] <= 64, r
     # nothing of the new unit is counted among the pinned namespaces
-    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 3
+    assert sum(r["name"].startswith("uavx_critic_grad_k::") for r in rows) == 5      # grad_combine, and each tile of grad_rows unweighted and weighted
     assert sum(r["name"].startswith("uavx_optim_k::") for r in rows) == 3
     assert not any("critic_fwd<" in r["name"] or "actor_fwd<" in r["name"] for r in mine)
 

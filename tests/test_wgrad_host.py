@@ -1,9 +1,9 @@
-"""Host-side checks of the weighted critic-loss gradient (libuavx_wgrad.so, include/uavx_wcritic_grad.h): the
-library builds for gfx950 without a GPU and carries its source hash, which covers the files of actor_csrc/ it compiles;
-it exports exactly what its header declares; it refuses every bad argument before touching a device; its workspace is
-§14's; its kernels use no scratch and spill nothing, with the resources §24 documents; the two libraries it stands beside
-are untouched; the learners refuse a bad per_beta on the host; and the float64 reference the GPU tests trust
-(wgrad_ref.py) is grad_ref's autograd when every weight is 1."""
+"""Host-side checks of the weighted critic-loss gradient (a unit of libuavx_actor.so, include/uavx_wcritic_grad.h, DESIGN.md
+§24): its header and every file it includes are under the actor library's source hash; the library exports exactly what the
+header declares; it refuses every bad argument before touching a device; its workspace is §14's; the weighted row kernels
+use no scratch and spill nothing, with the resources §24 documents; no library of its own is left and the priority library
+is untouched; the learners refuse a bad per_beta on the host; and the float64 reference the GPU tests trust (wgrad_ref.py) is
+grad_ref's autograd when every weight is 1."""
 import ctypes
 import importlib.util
 import os
@@ -21,9 +21,9 @@ P = 64                            # a pointer that is never dereferenced: every 
 
 
 def _xlib():
-    from gym_uav_collision_avoidance_amd import _wgrad_lib
-    _wgrad_lib.build()
-    return _wgrad_lib
+    from gym_uav_collision_avoidance_amd import _actor_lib
+    _actor_lib.build()
+    return _actor_lib
 
 
 def _kernels():
@@ -35,49 +35,51 @@ def _kernels():
 
 # ---- the library ----------------------------------------------------------------------------------------------------------
 
-def test_library_cross_compiles_and_carries_its_source_hash():
+def test_the_unit_is_under_the_actor_librarys_source_hash():
     x = _xlib()
-    assert os.path.basename(x.LIB_PATH) == "libuavx_wgrad.so" and os.path.isfile(x.LIB_PATH)
-    assert x.HEADER == os.path.join(ROOT, "include", "uavx_wcritic_grad.h") and x.HEADER in x._sources()
+    assert os.path.basename(x.LIB_PATH) == "libuavx_actor.so" and os.path.isfile(x.LIB_PATH)
+    assert x.WGRAD_HEADER == os.path.join(ROOT, "include", "uavx_wcritic_grad.h") and x.WGRAD_HEADER in x._sources()
     names = [os.path.relpath(f, ROOT) for f in x._sources()]
     pkg = "gym_uav_collision_avoidance_amd"
-    for f in (f"{pkg}/wgrad_csrc/uavx_wcritic_grad.hip", f"{pkg}/actor_csrc/uavx_grad_common.hip",
+    for f in (f"{pkg}/actor_csrc/uavx_critic_grad.hip", f"{pkg}/actor_csrc/uavx_grad_common.hip",
               f"{pkg}/actor_csrc/uavx_grad_impl.hpp", f"{pkg}/actor_csrc/uavx_actor_impl.hpp", "include/uavx_actor.h",
-              "include/uavx_critic.h"):
+              "include/uavx_critic.h", "include/uavx_critic_grad.h"):
         assert f in names, f
-    # every file the translation units include is under the hash
-    seen = set()
-    for f in x._sources():
+    # every file the unit's translation unit includes, and every file those include, is under the hash
+    unit = os.path.join(x.CSRC, "uavx_critic_grad.hip")
+    assert '#include "../../include/uavx_wcritic_grad.h"' in open(unit).read()
+    seen, todo = set(), [unit]
+    while todo:
+        f = todo.pop()
         for inc in re.findall(r'#include "([^"]+)"', open(f).read()):
-            seen.add(os.path.normpath(os.path.join(os.path.dirname(f), inc)))
-    assert seen <= {os.path.normpath(f) for f in x._sources()}, seen
+            inc = os.path.normpath(os.path.join(os.path.dirname(f), inc))
+            if inc not in seen:
+                seen.add(inc)
+                todo.append(inc)
+    assert seen and seen <= {os.path.normpath(f) for f in x._sources()}, seen
     blob = open(x.LIB_PATH, "rb").read()
-    assert f"UAVX_WGRAD_SRC_HASH={x.source_hash()}".encode() + b"\0" in blob and b"gfx950" in blob
+    assert f"UAVX_ACTOR_SRC_HASH={x.source_hash()}".encode() + b"\0" in blob and b"gfx950" in blob
     assert x._up_to_date()
     mk = open(os.path.join(x.CSRC, "Makefile")).read()
-    flags = re.search(r"^HIPFLAGS \?= (.*)$", mk, re.M).group(1)
-    actor_mk = open(os.path.join(ROOT, pkg, "actor_csrc", "Makefile")).read()
-    assert flags == re.search(r"^HIPFLAGS \?= (.*)$", actor_mk, re.M).group(1)
-    assert "UAVX_WGRAD_SRC_HASH" in mk and "OUT ?= libuavx_wgrad.so" in mk and "SRCHASH ?=" in mk
-    assert "../actor_csrc/uavx_grad_common.hip" in mk
-    assert "libuavx_wgrad.so.tmp*" in open(os.path.join(ROOT, ".gitignore")).read().split()
+    assert "../../include/uavx_wcritic_grad.h" in re.search(r"^HDR := (.*)$", mk, re.M).group(1).split()
 
 
 def test_library_exports_exactly_what_the_header_declares():
     x = _xlib()
-    hdr = open(x.HEADER).read()
+    hdr = open(x.WGRAD_HEADER).read()
     declared = set(re.findall(r"\b(uavx_wcritic_grad[a-z_0-9]*)\s*\(", hdr))
-    assert declared == set(x.SYMBOLS) == {"uavx_wcritic_grad_version", "uavx_wcritic_grad_workspace_bytes",
+    assert declared == set(x.WGRAD_SYMBOLS) == {"uavx_wcritic_grad_version", "uavx_wcritic_grad_workspace_bytes",
                                           "uavx_wcritic_grad"}
-    assert x.SYMBOLS[0] == "uavx_wcritic_grad_version"
+    assert x.WGRAD_SYMBOLS[0] == "uavx_wcritic_grad_version" == x.UNITS[-1].version
+    assert x.UNITS[-1].word == "weighted critic-gradient" and x.UNITS[-1].functions.keys() == declared
     lib = x.load()
     for name in sorted(declared):
         assert hasattr(lib, name), name
-    assert lib.uavx_wcritic_grad_version() == x.ABI_VERSION == 1 and "#define UAVX_WCRITIC_GRAD_VERSION 1" in hdr
-    assert f"#define UAVX_WCRITIC_GRAD_MAX_ROWS {x.MAX_ROWS}" in hdr and x.MAX_ROWS == 262144
-    # the C symbols the dynamic table defines are those three: nothing else of the ABI's name space leaks out
+    assert lib.uavx_wcritic_grad_version() == x.WGRAD_ABI_VERSION == 1 and "#define UAVX_WCRITIC_GRAD_VERSION 1" in hdr
+    assert f"#define UAVX_WCRITIC_GRAD_MAX_ROWS {x.GRAD_MAX_ROWS}" in hdr and x.GRAD_MAX_ROWS == 262144
+    # the C symbols of the ABI's name space that the dynamic table defines are those three: nothing else of it leaks out
     out = subprocess.run(["nm", "-D", "--defined-only", x.LIB_PATH], capture_output=True, text=True, check=True).stdout
-    c_names = {l.split()[-1] for l in out.splitlines() if " T " in l and not l.split()[-1].startswith("_")}
+    c_names = {l.split()[-1] for l in out.splitlines() if " T " in l and l.split()[-1].startswith("uavx_wcritic")}
     assert c_names == declared, c_names
     # the header's numbers are the ones the binding and the other headers use
     for name, value in (("UAVX_WCRITIC_SAC", x.SAC), ("UAVX_WCRITIC_TD3", x.TD3), ("UAVX_WCRITIC_DDPG", x.DDPG),
@@ -88,12 +90,16 @@ def test_library_exports_exactly_what_the_header_declares():
         assert re.search(r"#define UAVX_WCRITIC_%s \(?%d\)?\n" % (name, value), hdr), name
 
 
-def test_the_pinned_libraries_are_untouched():
+def test_no_library_of_its_own_is_left_and_the_priority_library_is_untouched():
+    import gym_uav_collision_avoidance_amd as pkg
     from gym_uav_collision_avoidance_amd import _actor_lib, _prio_lib
-    assert _actor_lib.source_hash() == "a056e385b4f6651e"
-    assert _prio_lib.source_hash() == "3e2046d3591a64b0"        # its value at the commit before this library existed
-    assert len(_actor_lib.UNITS) == 10 and not any("wcritic" in os.path.basename(f) or "wgrad" in os.path.basename(f)
-                                                   for f in _actor_lib._sources() + _prio_lib._sources())
+    assert _prio_lib.source_hash() == "3e2046d3591a64b0"        # its value at the commit before the weighted gradient existed
+    assert len(_actor_lib.UNITS) == 11
+    assert not any("wcritic" in os.path.basename(f) or "wgrad" in os.path.basename(f) for f in _prio_lib._sources())
+    here = os.path.dirname(pkg.__file__)
+    assert not os.path.exists(os.path.join(here, "wgrad_csrc")) and not os.path.exists(os.path.join(here, "_wgrad_lib.py"))
+    assert importlib.util.find_spec("gym_uav_collision_avoidance_amd._wgrad_lib") is None
+    assert "wgrad" not in open(os.path.join(ROOT, ".gitignore")).read()
 
 
 def _call(lib, kind=0, h1=256, h2=256, towers=2, loss=0, params=True, state=P, rows=4, ss=10, action=P, as_=2, y=P, ys=1,
@@ -177,13 +183,14 @@ def test_workspace_bytes_are_section_14s():
 
 
 def test_kernels_use_no_scratch_and_spill_nothing():
-    rows = _kernels()
-    assert sorted(r["name"] for r in rows) == ["uavx_grad_k::grad_weights", "uavx_wgrad_k::wgrad_combine",
-                                               "uavx_wgrad_k::wgrad_rows<false, 16>", "uavx_wgrad_k::wgrad_rows<true, 25>"]
-    # kernel -> (LDS bytes, VGPRs, AGPRs) as DESIGN.md §24 documents them: the row pass keeps grad_rows' budget (one
-    # workgroup per CU: 216 registers for the twins, 360 + 136 for DDPG), grad_weights is the actor library's kernel
-    documented = {"wgrad_rows<false, 16>": (83584, 216, 64), "wgrad_rows<true, 25>": (129664, 360, 136),
-                  "grad_weights": (0, 92, 64), "wgrad_combine": (0, 14, 0)}
+    unit = ("uavx_critic_grad_k::grad_combine", "uavx_critic_grad_k::grad_rows<false, 16, true>",
+            "uavx_critic_grad_k::grad_rows<true, 25, true>", "uavx_grad_k::grad_weights")
+    rows = [r for r in _kernels() if r["name"] in unit]
+    assert sorted(r["name"] for r in rows) == sorted(unit)
+    # kernel -> (LDS bytes, VGPRs, AGPRs) as DESIGN.md §24 documents them: the weighted row pass keeps the unweighted one's
+    # budget (one workgroup per CU: 216 registers for the twins, 360 + 136 for DDPG); the other two launches are shared
+    documented = {"grad_rows<false, 16, true>": (83584, 216, 64), "grad_rows<true, 25, true>": (129664, 360, 136),
+                  "grad_weights": (0, 92, 64), "grad_combine": (0, 14, 0)}
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     for r in rows:
         short = r["name"].split("::")[1]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Times the weighted critic-loss gradient (libuavx_wgrad.so) beside the unweighted one it restates, and a
-prioritized learner's update with and without the weighted loss, all graph-captured:
+"""Times the weighted critic-loss gradient (uavx_wcritic_grad) beside the unweighted one it shares its row
+pass with, and a prioritized learner's update with and without the weighted loss, all graph-captured:
 
   (a) FusedCriticLoss.backward(s, a, y, weight=w, q_out=q) against backward(s, a, y), per learner and batch size.  The
       unweighted baseline is timed twice (base_a, base_b): the spread between the two is the noise margin a difference has
@@ -10,7 +10,7 @@ prioritized learner's update with and without the weighted loss, all graph-captu
 
 The variants are timed in turn, three rounds of them, so that a drift of the machine hits all alike; every figure is
 [min, median, max] over the rounds of critic_bench.time_us (itself the median of three timed loops).  One JSON line per
-measurement, carrying the library's wgrad_sha; all of them also go to profiles/wgrad_bench.json.
+measurement, carrying the library's actor_sha; all of them also go to profiles/wgrad_bench.json.
 
     python tools/wgrad_bench.py [--rows 256 262144] [--kinds sac ddpg] [--iters 200] [--update-rows 256]
 """
@@ -25,7 +25,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 from critic_bench import time_us                                                        # noqa: E402
-from gym_uav_collision_avoidance_amd import BatchedMultiUAVWorld2D, _wgrad_lib, learners, policy  # noqa: E402
+from gym_uav_collision_avoidance_amd import BatchedMultiUAVWorld2D, _actor_lib, learners, policy  # noqa: E402
 from gym_uav_collision_avoidance_amd.fused_critic import FusedCriticLoss                # noqa: E402
 from gym_uav_collision_avoidance_amd.replay import DeviceReplay                         # noqa: E402
 
@@ -118,7 +118,7 @@ def main():
     lines = []
 
     def emit(res):
-        res["wgrad_sha"] = _wgrad_lib.source_hash()
+        res["actor_sha"] = _actor_lib.source_hash()
         lines.append(res)
         print(json.dumps(res), flush=True)
 
