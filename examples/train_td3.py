@@ -19,6 +19,7 @@ import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from gym_uav_collision_avoidance_amd import UAVVectorEnv
+from gym_uav_collision_avoidance_amd.checkpoint import load_run, save_run
 from gym_uav_collision_avoidance_amd.learners import FusedTD3
 from gym_uav_collision_avoidance_amd.replay import DeviceReplay
 
@@ -48,11 +49,19 @@ ap.add_argument("--per-beta-final", type=float, default=None, metavar="B1",
                 help="anneal the exponent linearly to this value over the run (default: keep B0)")
 ap.add_argument("--max-grad-norm", type=float, default=None, metavar="X",
                 help="clip the global gradient norm of the critic's and the actor's optimiser step to X (DESIGN.md §26)")
+ap.add_argument("--save-run", type=str, default=None, metavar="FILE",
+                help="write the whole run (worlds, ring, learner, exploration, generator, step) to FILE at the end (DESIGN.md §27)")
+ap.add_argument("--save-every", type=int, default=0, metavar="K", help="also write --save-run's FILE every K env steps")
+ap.add_argument("--resume", type=str, default=None, metavar="FILE",
+                help="continue the run saved in FILE, built from the same arguments, up to --steps steps in all")
 args = ap.parse_args()
 if args.per_beta_final is not None and not args.per_beta > 0:
     ap.error("--per-beta-final anneals a weighted loss: give --per-beta B0 > 0 with it")
+if args.save_every and not args.save_run:
+    ap.error("--save-every writes --save-run's file: give --save-run FILE with it")
 
 dev = torch.device("cuda", 0)
+torch.manual_seed(args.seed)           # the networks' initial weights: a run and the same run started again begin alike
 venv = UAVVectorEnv(args.envs, num_agents=args.agents, device=dev, seed=args.seed)
 mem = DeviceReplay(venv.env, horizon=args.horizon)
 mem.begin(venv.reset())
@@ -62,11 +71,16 @@ agent = FusedTD3(device=dev, generator=gen, memory=mem, n_step=args.n_step, rece
                  max_grad_norm=args.max_grad_norm)
 explore = agent.exploration(mem, seed=args.seed, warmup_steps=args.warmup, noise_std=args.noise_std)
 
+run = dict(env=venv.env, memory=mem, agent=agent, exploration=explore, generator=gen)
+first = 0                  # env steps the run had done when it was saved: warm-up, the anneal and the reports read t
+if args.resume:
+    first = int(load_run(args.resume, **run)["t"])
+    print(f"resumed {args.resume} at step {first}")
 t0 = time.perf_counter()
-for t in range(args.steps):
+for t in range(first, args.steps):
     agent.select_action(mem.state, explore=explore, out=mem.action_slot())     # forward + exploration, into the ring's slot
     mem.step(polar=True, auto_reset="agent0_done", step_cap=1500, track_returns=True)
-    if t + 1 == args.warmup:
+    if t + 1 == args.warmup or (args.resume and t == first and t + 1 > args.warmup):   # a resumed run captures again
         agent.capture(args.batch)                                              # sampling + the whole update, one graph
     if t + 1 >= args.warmup:
         if args.per_beta_final is not None:                                    # a device slot: the captured update follows it
@@ -78,8 +92,12 @@ for t in range(args.steps):
                                                    f"({norms['critic'][2] / agent.updates:.0%} of steps clipped)")
         q1, q2, pi = rows[0, :3]
         print(f"step {t + 1}: {agent.updates} updates, critic {q1:.4f} {q2:.4f} actor {pi:.4f}, "
-              f"{(t + 1) * args.envs / (time.perf_counter() - t0):,.0f} env steps/s{clip}")
+              f"{(t + 1 - first) * args.envs / (time.perf_counter() - t0):,.0f} env steps/s{clip}")
+    if args.save_every and (t + 1) % args.save_every == 0 and t + 1 < args.steps:
+        save_run(args.save_run, **run, extra={"t": t + 1})
 torch.cuda.synchronize()
+if args.save_run:
+    print("wrote", save_run(args.save_run, **run, extra={"t": max(first, args.steps)}))
 st = venv.episode_stats()
 print(f"{int(st['episodes'].sum())} episodes ended: {int(st['reach'].sum())} reached the goal, {int(st['coll'].sum())} collided")
 if args.checkpoint:

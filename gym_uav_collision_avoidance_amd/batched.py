@@ -542,7 +542,9 @@ class BatchedMultiUAVWorld2D(_Base):
         curriculum / staging parameters), "host": the few Python-side values (seed, constructor shape)}.  The reference
         checkpoints only its agents (sac.py:101-139); with this a 65 536-env run resumes where it stopped.  torch.save-able."""
         n = int(self._L.uavx_snapshot_bytes(self._h))
-        blob = torch.empty((n + 256,), dtype=torch.uint8, device=self.device)
+        # zeros, not empty: uavx_save leaves the header's padding and, outside the float64-position mode, the room of those
+        # arrays unwritten, and equal states must give equal bytes (checkpoint.py compares and stores them)
+        blob = torch.zeros((n + 256,), dtype=torch.uint8, device=self.device)
         off = (-blob.data_ptr()) % 256                       # uavx_save wants a 256-byte aligned buffer
         snap = blob[off:off + n]
         _lib.check(self._L.uavx_save(self._h, snap.data_ptr(), self._stream()), self._h)

@@ -16,6 +16,7 @@ pytorch_ddpg_temp/ddpg.py) with every step of update_parameters as HIP launches 
     agent.capture(256); agent.run(1000)                # the same update as a captured graph, replayed
     agent.losses(last=10)                              # the ONE host read: [n, 8] rows of the loss ring, in update order
     a = agent.select_action(mem.state)                 # FusedActor.act on the live actor
+    sd = agent.state_dict(); agent.load_state_dict(sd) # the whole learner, for checkpoint.save_run / load_run (§27)
 
 A row of the loss ring holds critic_loss_1, critic_loss_2 (0 for DDPG), actor_loss (0 in an update without an actor
 step), alpha_loss, alpha, actor_updated, 0, 0: what the reference's update_parameters returns through .item().
@@ -541,6 +542,102 @@ class _FusedLearner:
             h.refresh()
         return self
 
+    # ---- the whole learner, for a run that stops and continues (checkpoint.py) ---------------------------
+    def _nets(self):
+        """{attribute name: module} of every network and target."""
+        raise NotImplementedError
+
+    def _optims(self):
+        """{attribute name of the torch optimiser: its FusedAdam}."""
+        raise NotImplementedError
+
+    def _config_extra(self):
+        return {}
+
+    def _config(self):
+        """What a saved learner must share with the one it is loaded into: checked by load_state_dict, never applied."""
+        cfg = {"class": type(self).__name__, "dims": dict(self._dims), "log_capacity": self.log_capacity,
+               "n_step": self.n_step, "recency": self.recency, "prioritized": self.prioritized, "per_eps": self.per_eps,
+               "per_n_step": self.per_n_step, "weighted": self._per_weighted,
+               "clips": [a.max_grad_norm is not None for a in self._adams()]}
+        cfg.update(self._config_extra())
+        return cfg
+
+    def state_dict(self, include_sampler=True):
+        """Everything a bit-exact continuation of this learner needs, on the CPU, as tensors and built-in types: the
+        modules, the optimisers' state (device step counts synced first, as save_checkpoint does), `updates`, the whole
+        loss-ring allocation (loss rows, the device update count, both clip records with their bounds), per_beta,
+        max_grad_norm, the attached prioritized sampler's state (include_sampler=False leaves it out; the uniform and
+        n-step samplers have none) and the configuration load_state_dict validates.  It synchronises: keep it out of the
+        update loop."""
+        optims = self._optims()
+        for adam in optims.values():
+            adam.sync_state()
+        sampler = None
+        if include_sampler and isinstance(self._sampler, PrioritizedReplaySampler):
+            sampler = self._sampler.state_dict()
+        return {"config": self._config(),
+                "modules": {name: _cpu(m.state_dict()) for name, m in self._nets().items()},
+                "optimizers": {name: _cpu(adam.optimizer.state_dict()) for name, adam in optims.items()},
+                "updates": int(self.updates), "ring": self._ring.detach().cpu().clone(), "per_beta": float(self.per_beta),
+                "max_grad_norm": list(self.max_grad_norm), "sampler": sampler}
+
+    def _check_state(self, sd):
+        """Refuses a state_dict() this learner cannot continue, naming the field, before load_state_dict writes anything."""
+        who, mine = type(self).__name__, self._config()
+        saved = sd.get("config")
+        if not isinstance(saved, dict):
+            raise ValueError(f"uavx: {who}.load_state_dict takes a learner's state_dict(): no configuration block")
+        for field in ("class",) + tuple(k for k in mine if k != "class"):
+            if field not in saved or saved[field] != mine[field]:
+                raise ValueError(f"uavx: the saved learner has {field} = {saved.get(field)!r}, this {who} {field} = "
+                                 f"{mine[field]!r}")
+        for part, names in (("modules", self._nets()), ("optimizers", self._optims())):
+            if not isinstance(sd.get(part), dict) or set(sd[part]) != set(names):
+                raise ValueError(f"uavx: the saved learner's {part} are {sorted(sd.get(part) or ())}, this {who}'s "
+                                 f"{sorted(names)}")
+        ring = sd.get("ring")
+        if not torch.is_tensor(ring) or ring.dtype != torch.float32 or tuple(ring.shape) != tuple(self._ring.shape):
+            raise ValueError(f"uavx: the saved loss ring does not have this {who}'s {tuple(self._ring.shape)} float32 layout")
+        self._check_per_beta(sd["per_beta"])
+        self._check_max_grad_norm(sd["max_grad_norm"])
+        if sd.get("sampler") is not None:
+            if not isinstance(self._sampler, PrioritizedReplaySampler):
+                raise ValueError(f"uavx: the saved learner carries a priority table: attach() a DeviceReplay to this {who} "
+                                 f"before loading it")
+            table = sd["sampler"]["table"]
+            if tuple(table.shape) != tuple(self._sampler._table.shape):
+                raise ValueError(f"uavx: the saved priority table is {tuple(table.shape)}, this ring's "
+                                 f"{tuple(self._sampler._table.shape)}")
+
+    def _load_extra(self, sd):
+        """What a subclass keeps besides modules and optimisers."""
+
+    def load_state_dict(self, sd):
+        """Restores a state_dict() of a learner of the same class and configuration.  A mismatch is refused with a message
+        that names the field, before anything is written.  Parameters, the loss ring and the sampler's table are written
+        in place; every fused handle is re-packed, and captured graphs are dropped (they hold the addresses of the optimiser
+        state this call replaced): capture() again before run()."""
+        self._check_state(sd)
+        for name, m in self._nets().items():
+            m.load_state_dict(sd["modules"][name])
+        for name, adam in self._optims().items():
+            adam.load_state_dict(sd["optimizers"][name])
+        self._load_extra(sd)
+        self._ring.copy_(sd["ring"])
+        self.updates = int(sd["updates"])
+        if self._per_weighted:
+            self.set_per_beta(sd["per_beta"])
+        if any(b is not None for b in sd["max_grad_norm"]):
+            self.set_max_grad_norm(tuple(sd["max_grad_norm"]))
+        if sd.get("sampler") is not None:
+            self._sampler.load_state_dict(sd["sampler"])
+        self._graphs = None
+        return self._repack()
+
+    def _repack(self):
+        return self.refresh()
+
     def close(self):
         for x in self._handles():
             x.close()
@@ -602,6 +699,39 @@ class FusedSAC(_FusedLearner):
 
     def _packed(self):
         return (self._actor_h, self._target_h)
+
+    def _nets(self):
+        return {"policy": self.policy, "critic": self.critic, "critic_target": self.critic_target}
+
+    def _optims(self):
+        out = {"critic_optim": self._critic_adam, "policy_optim": self._policy_adam}
+        if self.automatic_entropy_tuning:
+            out["alpha_optim"] = self._alpha_adam
+        return out
+
+    def _config_extra(self):
+        return {"automatic_entropy_tuning": self.automatic_entropy_tuning,
+                "target_update_interval": self.target_update_interval}
+
+    def state_dict(self, include_sampler=True):
+        sd = super().state_dict(include_sampler)
+        sd["alpha"] = self._alpha.detach().cpu().clone()
+        if self.automatic_entropy_tuning:
+            sd["log_alpha"] = self.log_alpha.detach().cpu().clone()
+        return sd
+
+    def _check_state(self, sd):
+        super()._check_state(sd)
+        for name in ("alpha",) + (("log_alpha",) if self.automatic_entropy_tuning else ()):
+            t = sd.get(name)
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or tuple(t.shape) != (1,):
+                raise ValueError(f"uavx: the saved learner's {name} must be a float32 tensor of one element")
+
+    def _load_extra(self, sd):
+        self._alpha.copy_(sd["alpha"])
+        if self.automatic_entropy_tuning:
+            with torch.no_grad():
+                self.log_alpha.copy_(sd["log_alpha"])
 
     @property
     def alpha(self):
@@ -697,6 +827,18 @@ class _ActorCriticLearner(_FusedLearner):
     def _packed(self):
         return (self._actor_h, self._target)
 
+    def _nets(self):
+        return {"actor": self.actor, "actor_target": self.actor_target, "critic": self.critic,
+                "critic_target": self.critic_target}
+
+    def _optims(self):
+        return {"critic_optimizer": self._critic_adam, "actor_optimizer": self._actor_adam}
+
+    def _repack(self):
+        self.refresh()                      # select_action's lazily re-packed actor included: it is current now
+        self._stale = False
+        return self
+
     def _actor_and_targets(self, s):
         """The actor update and both soft updates, the actor's first (td3.py:141-156, ddpg.py:73-83) -> the actor loss."""
         actor_loss = self._pgrad.backward(s)
@@ -767,6 +909,9 @@ class FusedTD3(_ActorCriticLearner):
 
     def _discount(self):
         return self.discount
+
+    def _config_extra(self):
+        return {"policy_freq": self.policy_freq}
 
     def _variants(self):
         return (True,) if self.policy_freq == 1 else (True, False)

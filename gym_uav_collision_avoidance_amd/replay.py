@@ -43,6 +43,43 @@ class DeviceReplay:
     def __len__(self):
         return min(self.count, self.T) * self.env.num_envs * self.num_learners
 
+    # -- snapshot / restore (checkpoint.py) -----------------------------------------------------------------
+    _RING = ("obs", "act", "rew", "done", "skip", "trunc", "ended")
+
+    def _facts(self):
+        return {"L": self.L, "num_envs": self.env.num_envs, "num_agents": self.env.num_agents,
+                "num_learners": self.num_learners, "packed": self.packed}
+
+    def state_dict(self):
+        """CPU copies of the seven ring tensors, `count`, and the shape facts load_state_dict checks (L, num_envs,
+        num_agents, num_learners, packed).  The copies synchronise; keep the call out of the step loop."""
+        sd = {name: getattr(self, name).detach().cpu().clone() for name in self._RING}
+        sd["count"] = int(self.count)
+        sd.update(self._facts())
+        return sd
+
+    def load_state_dict(self, sd):
+        """Restores a state_dict() of a ring of the same shape and flag packing IN PLACE (copy_): samplers, ctypes structs
+        and captured graphs that hold the ring's addresses stay valid.  Anything else is refused before a byte is written."""
+        for field, mine in self._facts().items():
+            if field not in sd:
+                raise ValueError(f"uavx: the saved ring has no {field!r}")
+            if type(sd[field]) is not type(mine) or sd[field] != mine:
+                raise ValueError(f"uavx: the saved ring has {field} = {sd[field]!r}, this one {field} = {mine!r}")
+        for name in self._RING:
+            t, mine = sd.get(name), getattr(self, name)
+            if not torch.is_tensor(t) or t.dtype != mine.dtype or tuple(t.shape) != tuple(mine.shape):
+                got = f"{t.dtype} {tuple(t.shape)}" if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"uavx: the saved ring tensor {name!r} is {got}, this ring's is {mine.dtype} "
+                                 f"{tuple(mine.shape)}")
+        count = sd.get("count")
+        if isinstance(count, bool) or not isinstance(count, int) or count < 0:
+            raise ValueError(f"uavx: the saved ring has count = {count!r}, not a step count")
+        for name in self._RING:
+            getattr(self, name).copy_(sd[name])
+        self.count = count
+        return self
+
     def begin(self, obs0):
         """Stores the observation the first step starts from (what env.reset() returned)."""
         self.obs[self.count % self.L].copy_(obs0)
