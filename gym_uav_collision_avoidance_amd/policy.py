@@ -38,6 +38,20 @@ class GaussianPolicy(nn.Module):
         return torch.tanh(mean + log_std.exp() * eps)
 
 
+class ValueNet(nn.Module):
+    """State value V(s) for the on-policy learner (ppo.py): 10 -> 256 -> 256 -> 1, ReLU.  The reference has
+    no such network; the names follow its GaussianPolicy."""
+
+    def __init__(self, num_inputs=10, hidden=256):
+        super().__init__()
+        self.linear1 = nn.Linear(num_inputs, hidden)
+        self.linear2 = nn.Linear(hidden, hidden)
+        self.linear3 = nn.Linear(hidden, 1)
+
+    def forward(self, state):
+        return self.linear3(F.relu(self.linear2(F.relu(self.linear1(state)))))
+
+
 def load_reference_checkpoint(path, device="cuda", num_inputs=10, num_actions=2):
     """Loads the policy part of a reference `weights.chpt` (tensors only: weights_only=True)."""
     ckpt = torch.load(path, map_location=device, weights_only=True)

@@ -1,0 +1,192 @@
+"""PPO on the device ring: the on-policy learner for tens of thousands of parallel worlds.
+
+    mem = DeviceReplay(venv.env, horizon=32)
+    mem.begin(venv.reset())
+    ppo = PPO(mem, generator=gen)
+    for it in range(iterations):
+        for _ in range(32):
+            ppo.act()                                   # tanh(μ + σ·ε) into the ring's action slot
+            mem.step(polar=True, auto_reset="agent0_done", step_cap=1500)
+        losses = ppo.update()                           # 0-d device tensors
+
+The rollout IS the ring: act() writes its action into the slot the step launch reads and keeps the pre-squash sample u and
+log π(a|s) in two buffers of the ring's shape; update() evaluates the value net over the whole ring in one forward, takes
+advantages and returns from rollout.RolloutAdvantages (one HIP walk, libuavx_gae.so) and runs epochs × minibatches steps of
+the clipped surrogate.  The networks and their update are plain torch autograd: minibatches of tens of thousands of rows are
+the regime where torch's GEMMs are the right tool (README, large-batch figures), so no hand kernel replaces them.
+
+Nothing in update() reads the device from the host, so the set of rows cannot shrink to the valid ones: every (step, env,
+learner) row of the window is a row of the batch, and a 0/1 weight takes out what is not a sample -- re-initialisation rows
+(valid = 0) and rows of an agent that was already done before the step (parked in an env that went on: the previous row's
+done, unless that row ended the episode or was a re-initialisation).  Every mean below is Σ w·x / max(1, Σ w)."""
+import math
+
+import torch
+
+from .policy import GaussianPolicy, ValueNet
+from .rollout import RolloutAdvantages
+
+_LOG_2PI = math.log(2.0 * math.pi)
+_LOG_2 = math.log(2.0)
+
+
+def log_prob(mean, log_std, u):
+    """log π(tanh(u)) of the tanh-squashed Gaussian, summed over the action dimensions: the Gaussian's log density at u
+    minus log|d tanh(u)/du| in its stable form 2·(log 2 − u − softplus(−2u))."""
+    z = (u - mean) * torch.exp(-log_std)
+    gauss = -0.5 * z * z - log_std - 0.5 * _LOG_2PI
+    squash = 2.0 * (_LOG_2 - u - torch.nn.functional.softplus(-2.0 * u))
+    return (gauss - squash).sum(-1)
+
+
+def _positive(name, x, integer=False):
+    ok = not isinstance(x, bool) and isinstance(x, int if integer else (int, float)) and x > 0 and math.isfinite(x)
+    if not ok:
+        raise ValueError(f"uavx: PPO: {name} must be a finite {'int' if integer else 'float'} > 0, got {x!r}")
+    return x
+
+
+class PPO:
+    def __init__(self, mem, generator=None, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5,
+                 ent_coef=0.0, max_grad_norm=0.5, rollout=None):
+        """mem: the DeviceReplay the rollout is collected in (its horizon bounds the rollout; num_learners is respected).
+        generator: a torch.Generator on the ring's device for the action noise and the minibatch permutations.
+        rollout: steps per update, default the ring's horizon.  max_grad_norm: None = no clipping."""
+        _positive("lr", lr), _positive("clip", clip)
+        self.epochs, self.minibatches = _positive("epochs", epochs, True), _positive("minibatches", minibatches, True)
+        for name, x in (("vf_coef", vf_coef), ("ent_coef", ent_coef)):
+            if isinstance(x, bool) or not isinstance(x, (int, float)) or not math.isfinite(x) or x < 0:
+                raise ValueError(f"uavx: PPO: {name} must be a finite float >= 0, got {x!r}")
+        if max_grad_norm is not None:
+            _positive("max_grad_norm", max_grad_norm)
+        self.rollout = mem.T if rollout is None else _positive("rollout", rollout, True)
+        if self.rollout > mem.T:
+            raise ValueError(f"uavx: PPO: rollout = {self.rollout} steps do not fit the ring's horizon of {mem.T}")
+        self.mem, self.generator = mem, generator
+        self.clip, self.vf_coef, self.ent_coef, self.max_grad_norm = float(clip), float(vf_coef), float(ent_coef), max_grad_norm
+        self.advantages = RolloutAdvantages(mem, gamma=gamma, lam=lam, normalize=True)
+        self.device = dev = mem.rew.device
+        rows = self.rollout * mem.env.num_envs * mem.num_learners
+        if rows % self.minibatches:
+            raise ValueError(f"uavx: PPO: {self.minibatches} minibatches do not divide the {rows} rows of a rollout")
+        self.policy = GaussianPolicy().to(dev)
+        self.value = ValueNet().to(dev)
+        self.params = list(self.policy.parameters()) + list(self.value.parameters())
+        self.optimizer = torch.optim.Adam(self.params, lr=lr)
+        L, E, N = self.advantages.shape
+        self.u = torch.zeros((L, E, N, 2), dtype=torch.float32, device=dev)     # pre-squash sample of the slot's action
+        self.logp = torch.zeros((L, E, N), dtype=torch.float32, device=dev)     # log π of it under the policy that drew it
+        self.updates = 0
+        self.values = None            # what the last update() gave RolloutAdvantages
+        self.first_ratio = None       # π / π_old over the first minibatch of the last update()'s first epoch
+
+    # -- acting --------------------------------------------------------------------------------------------------------------
+    @torch.no_grad()
+    def act(self):
+        """Samples u = μ + σ·ε for the ring's current state, writes tanh(u) into mem.action_slot() (returned) and keeps u and
+        log π at the slot: call mem.step() next."""
+        mem = self.mem
+        s = mem.count % mem.L
+        mean, log_std = self.policy(mem.state)
+        eps = torch.randn(mean.shape, generator=self.generator, device=mean.device, dtype=mean.dtype)
+        u = mean + log_std.exp() * eps
+        self.u[s].copy_(u)
+        self.logp[s].copy_(log_prob(mean, log_std, u))
+        out = mem.action_slot()
+        torch.tanh(u, out=out)
+        return out
+
+    @torch.no_grad()
+    def select_action(self, obs, evaluate=True):
+        """obs [..., 10] -> actions [..., 2] in [-1, 1] without touching the ring (evaluate.py's policy_fn)."""
+        return self.policy.act(obs, evaluate=evaluate, generator=self.generator)
+
+    # -- learning ------------------------------------------------------------------------------------------------------------
+    def _parked(self, slots, first_k):
+        """[steps, E, learners] bool: the agent was already done before the step of that row."""
+        mem = self.mem
+        prev = (slots - 1) % mem.L
+        skip, _, ended = mem._flags(prev, slice(None))
+        parked = ((mem.done[prev] & 1) != 0) & ~(ended | skip).unsqueeze(-1)
+        if first_k == 0:
+            parked[0] = False         # the ring's first step has no row before it
+        return parked[:, :, :mem.num_learners]
+
+    def update(self):
+        """One PPO update over the last `rollout` steps of the ring (fewer while the ring holds fewer).  Returns a dict of 0-d
+        device tensors (means over the last epoch's minibatches); nothing is read on the host."""
+        mem, nl = self.mem, self.mem.num_learners
+        steps = min(self.rollout, mem.count, mem.T)
+        with torch.no_grad():
+            self.values = self.value(mem.obs).squeeze(-1).contiguous()
+        out = self.advantages.compute(self.values, steps)
+        slots = self.advantages.window(steps)
+        take = lambda t: t[slots][:, :, :nl]
+        obs = take(mem.obs).reshape(-1, mem.obs.shape[-1])
+        u = take(self.u).reshape(-1, 2)
+        logp_old = take(self.logp).reshape(-1)
+        adv = take(out.adv_norm).reshape(-1)
+        ret = take(out.ret).reshape(-1)
+        weight = ((take(out.valid) != 0) & ~self._parked(slots, mem.count - steps)).reshape(-1).to(torch.float32)
+        rows = obs.shape[0]
+        size = rows // self.minibatches
+        log = {}
+        for epoch in range(self.epochs):
+            perm = torch.randperm(rows, generator=self.generator, device=self.device)
+            log = {"policy_loss": [], "value_loss": [], "entropy": []}
+            for j in range(self.minibatches):
+                idx = perm[j * size:(j + 1) * size]
+                w = weight[idx]
+                denom = w.sum().clamp(min=1.0)
+                mean, log_std = self.policy(obs[idx])
+                logp = log_prob(mean, log_std, u[idx])
+                ratio = torch.exp(logp - logp_old[idx])
+                if epoch == 0 and j == 0:
+                    self.first_ratio = ratio.detach()
+                a = adv[idx]
+                surrogate = torch.minimum(ratio * a, ratio.clamp(1.0 - self.clip, 1.0 + self.clip) * a)
+                policy_loss = -(w * surrogate).sum() / denom
+                v = self.value(obs[idx]).squeeze(-1)
+                value_loss = (w * (0.5 * (v - ret[idx]) ** 2)).sum() / denom
+                entropy = -(w * logp).sum() / denom          # the sample estimate: the squashed Gaussian has no closed form
+                loss = policy_loss + self.vf_coef * value_loss - self.ent_coef * entropy
+                self.optimizer.zero_grad(set_to_none=True)
+                loss.backward()
+                if self.max_grad_norm is not None:
+                    torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+                self.optimizer.step()
+                log["policy_loss"].append(policy_loss.detach())
+                log["value_loss"].append(value_loss.detach())
+                log["entropy"].append(entropy.detach())
+        self.updates += 1
+        return {k: torch.stack(v).mean() for k, v in log.items()}
+
+    # -- snapshot / restore (checkpoint.py) ---------------------------------------------------------------------
+    def state_dict(self, include_sampler=True):
+        """Tensors and built-in types only: the two networks, Adam's state, the per-slot u and log π (left out with
+        include_sampler=False, as the ring then is), the update count."""
+        sd = {"kind": "ppo", "policy": dict(self.policy.state_dict()), "value": dict(self.value.state_dict()),
+              "optimizer": self.optimizer.state_dict(), "updates": int(self.updates)}
+        if include_sampler:
+            sd["u"], sd["logp"] = self.u, self.logp
+        return sd
+
+    def load_state_dict(self, sd):
+        """Restores a state_dict() of a PPO of the same shapes, in place."""
+        if not isinstance(sd, dict) or sd.get("kind") != "ppo":
+            raise ValueError("uavx: PPO.load_state_dict was given the state of another learner")
+        for name in ("u", "logp"):
+            if name in sd and (not torch.is_tensor(sd[name]) or tuple(sd[name].shape) != tuple(getattr(self, name).shape)
+                               or sd[name].dtype != torch.float32):
+                raise ValueError(f"uavx: the saved PPO's {name!r} does not fit this ring")
+        self.policy.load_state_dict(sd["policy"])
+        self.value.load_state_dict(sd["value"])
+        self.optimizer.load_state_dict(sd["optimizer"])
+        for name in ("u", "logp"):
+            if name in sd:
+                getattr(self, name).copy_(sd[name])
+        self.updates = int(sd["updates"])
+        return self
+
+    def close(self):
+        pass
