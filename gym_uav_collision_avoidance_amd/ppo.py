@@ -79,6 +79,7 @@ class PPO:
         self.updates = 0
         self.values = None            # what the last update() gave RolloutAdvantages
         self.first_ratio = None       # π / π_old over the first minibatch of the last update()'s first epoch
+        self.weight = None            # the 0/1 weight of the last update()'s rows, (step oldest first, env, learner) order
 
     # -- acting --------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -127,7 +128,7 @@ class PPO:
         logp_old = take(self.logp).reshape(-1)
         adv = take(out.adv_norm).reshape(-1)
         ret = take(out.ret).reshape(-1)
-        weight = ((take(out.valid) != 0) & ~self._parked(slots, mem.count - steps)).reshape(-1).to(torch.float32)
+        self.weight = weight = ((take(out.valid) != 0) & ~self._parked(slots, mem.count - steps)).reshape(-1).to(torch.float32)
         rows = obs.shape[0]
         size = rows // self.minibatches
         log = {}

@@ -167,6 +167,60 @@ def big(E, N, T, learners=None, seed=70):
     return case
 
 
+ROWS = 8                 # rows of a column the walk fetches together; the layout below plants its events around multiples of it
+T_GROUPS = 3 * ROWS
+GROUP_STEPS = (ROWS - 1, ROWS, ROWS + 1, 2 * ROWS - 1, 2 * ROWS, 2 * ROWS + 1, 3 * ROWS - 1, 3 * ROWS)
+
+
+def row_groups(steps, wrapped, E=100, N=3, learners=2, seed=90):
+    """A ring of T = 24 (L = 25) whose events are planted by walk position j (j = 0 is the newest row, step count − 1):
+        env 0   skip at j = 7 (the last row of the first group of ROWS rows)
+        env 1   skip at j = 8 (the first row of the second group)
+        env 2   skip at j = 7 and at j = 8
+        env 3   ended at j = 8
+        env 4   agent 0 done at j = 15;  env 5: agent 1 done at j = 16
+        env 6   agent 0 parked (done = 1) in the rows j = 16 ... 8, alive again from j = 7
+        env 7   skip at j = 6 alone: the row at j = 8 is NOT cut (a cut taken from the wrong row of the first group would cut it;
+                behind a skip row itself the carry is 0 and a cut changes no value)
+    Envs 0-7 carry nothing else; every other env has dones, ended and skip rows at a rate of 3 %.  wrapped: count = 40, so
+    the window wraps around the ring; otherwise count = steps and the window's oldest row is the ring's step 0 (an event
+    whose j lies before step 0 is not planted)."""
+    assert E >= 9 and N >= 2 and 1 <= steps <= T_GROUPS
+    count = 40 if wrapped else steps
+    c = _base(E, N, T=T_GROUPS, count=count, steps=steps, learners=learners, seed=seed, p_done=0.03, p_ended=0.03, p_skip=0.03)
+    c["done"][:, :8], c["skip"][:, :8], c["ended"][:, :8] = 0, 0, 0
+    planted = [("skip", ROWS - 2, 7, None), ("skip", ROWS - 1, 0, None), ("skip", ROWS, 1, None), ("skip", ROWS - 1, 2, None), ("skip", ROWS, 2, None),
+               ("ended", ROWS, 3, None), ("done", 2 * ROWS - 1, 4, 0), ("done", 2 * ROWS, 5, 1)]
+    planted += [("done", j, 6, 0) for j in range(ROWS, 2 * ROWS + 1)]
+    for what, j, e, i in planted:
+        k = count - 1 - j
+        if k >= 0:
+            c[what][(_slot(c, k), e) if i is None else (_slot(c, k), e, i)] = 1
+    c["name"] = f"row_groups_s{steps}_{'wrapped' if wrapped else 'from0'}"
+    return c
+
+
+def ppo_ring(E=32, N=3, T=12, count=17, learners=2, seed=97):
+    """The ring of the PPO update tests: 32 x 3, T = 12, two learners, count = 17 (a wrapped window of 12 steps = 768 rows),
+    dones, ended and skip rows at 5 %, and planted in envs 0-2, which carry nothing else:
+        env 0   agent 0 done at k = 8 and parked (done = 1) up to k = 13, its env going on
+        env 1   agent 1 done at k = 9 and the env's episode ended in that row: its row at k = 10 is a sample again
+        env 2   re-initialisation rows at k = 6 and k = 7, the done bit of agent 0 set in the row at k = 7 (no step, so it
+                parks nobody: the row at k = 8 is a sample)"""
+    c = _base(E, N, T=T, count=count, learners=learners, seed=seed, p_done=0.05, p_ended=0.05, p_skip=0.05)
+    c["rew"] += np.float32(3)            # returns of one sign: an untrained value net's gradient norm is then above 1
+    c["done"][:, :3], c["skip"][:, :3], c["ended"][:, :3] = 0, 0, 0
+    for k in range(8, 14):
+        c["done"][_slot(c, k), 0, 0] = 1
+    c["done"][_slot(c, 9), 1, 1] = 1
+    c["ended"][_slot(c, 9), 1] = 1
+    c["skip"][_slot(c, 6), 2] = 1
+    c["skip"][_slot(c, 7), 2] = 1
+    c["done"][_slot(c, 7), 2, 0] = 1
+    c["name"] = "ppo_ring"
+    return c
+
+
 def packed(case):
     """The same ring with the flags in agent 0's done byte: bit 1 skip, bit 2 ended; bit 3 (truncated) set on every third
     ended row.  Returns a new case whose skip and ended are None."""

@@ -1,7 +1,9 @@
 """Host-side checks of GAE(λ) over the ring (libuavx_gae.so, include/uavx_gae.h): the numpy restatement the
 GPU tests trust (gae_ref.py) equals a second, per-column writing of the header's prose bit for bit on every crafted layout,
 agrees with the textbook special cases (λ = 0: the one-step TD error; λ = 1 without cuts: the discounted return) and its
-documented summation order with numpy's two-pass standard deviation; the library builds for gfx950 without a GPU, carries
+documented summation order with numpy's two-pass standard deviation; the two writings also agree on the row-group windows,
+the straddled shapes and past 256 partials (the shapes of test_gpu_gae.py), and the restatement is held to the definition of
+GAE(λ) itself, the forward view summed in exact rational arithmetic (gae_forward.py), within a derived bound; the library builds for gfx950 without a GPU, carries
 its source hash, exports exactly what its header declares and refuses every bad argument before touching a device; the other
 libraries keep their pinned hashes; the Python layer refuses bad arguments on the host and a PPO's state is plain data."""
 import ctypes
@@ -123,6 +125,150 @@ def test_documented_summation_order_against_numpy_two_pass_std(case):
     print(f"{case}: n = {n}, std = {std!r}, numpy = {want!r}, relative difference {abs(std - want) / want:.3e}, bound {bound:.3e}")
     assert abs(std - want) <= bound * want
     assert abs(mean - a.mean()) <= bound * max(abs(a.mean()), np.abs(a).mean())
+
+
+# ---- windows around the groups of rows the walk fetches together -------------------------------------------------------------
+
+def _restatement_equals_the_loop(case):
+    kw = gae_layouts.ref_args(case)
+    adv, ret, valid = gae_ref.gae(fill=7, **kw)
+    adv2, ret2, valid2 = gae_ref.gae_loop(fill=7, **kw)
+    assert same(adv, adv2) and same(ret, ret2) and same(valid, valid2)
+    st, st2 = gae_ref.stats(adv, valid, case["count"], case["steps"]), gae_ref.stats_loop(adv, valid, case["count"], case["steps"])
+    assert st[0] == st2[0] > 0 and same(np.float64(st[1:]), np.float64(st2[1:])), (st, st2)
+
+
+@pytest.mark.parametrize("flags", ["rows", "packed"])
+@pytest.mark.parametrize("wrapped", [True, False], ids=["count40", "count_steps"])
+@pytest.mark.parametrize("steps", gae_layouts.GROUP_STEPS)
+def test_restatement_equals_the_loop_around_the_row_groups(steps, wrapped, flags):
+    case = gae_layouts.row_groups(steps, wrapped)
+    _restatement_equals_the_loop(gae_layouts.packed(case) if flags == "packed" else case)
+
+
+@pytest.mark.parametrize("flags", ["rows", "packed"])
+@pytest.mark.parametrize("shape", [(300, 1, None), (100, 3, None), (60, 5, 3), (40, 7, 1)], ids=["300x1", "100x3", "60x5_l3", "40x7_l1"])
+def test_restatement_equals_the_loop_with_envs_across_wavefront_edges(shape, flags):
+    case = gae_layouts.big(shape[0], shape[1], 12, learners=shape[2], seed=73)
+    _restatement_equals_the_loop(gae_layouts.packed(case) if flags == "packed" else case)
+
+
+def test_row_group_layout_holds_what_its_docstring_says():
+    R = gae_layouts.ROWS
+    assert R == 8 and gae_layouts.T_GROUPS == 24 and gae_layouts.GROUP_STEPS == (7, 8, 9, 15, 16, 17, 23, 24)
+    for wrapped in (True, False):
+        c = gae_layouts.row_groups(24, wrapped)
+        assert (c["T"], c["E"], c["N"], c["learners"], c["steps"], c["count"]) == (24, 100, 3, 2, 24, 40 if wrapped else 24)
+        L = c["T"] + 1
+        row = lambda name, j: c[name][(c["count"] - 1 - j) % L]               # the row at walk position j
+        skips = {e: [j for j in range(24) if row("skip", j)[e]] for e in range(8)}
+        assert skips == {0: [7], 1: [8], 2: [7, 8], 3: [], 4: [], 5: [], 6: [], 7: [6]}
+        assert {e: [j for j in range(24) if row("ended", j)[e]] for e in range(8)} == {e: [8] if e == 3 else [] for e in range(8)}
+        dones = {(e, i): [j for j in range(24) if row("done", j)[e, i]] for e in range(8) for i in range(3)}
+        assert {q: js for q, js in dones.items() if js} == {(4, 0): [15], (5, 1): [16], (6, 0): list(range(8, 17))}
+        assert c["skip"][:, 8:].any() and c["ended"][:, 8:].any() and c["done"][:, 8:].any()      # the low-rate rest
+        assert 0.005 < c["skip"][:, 8:].mean() < 0.08
+        adv, ret, valid = gae_ref.gae(**gae_layouts.ref_args(c))
+        # what the events do to the walk: a skip row cuts the row before it and restarts the carry after it
+        s7, s8, s9 = [(c["count"] - 1 - j) % L for j in (7, 8, 9)]
+        assert not valid[s7, 0].any() and valid[s8, 0, :2].all() and not valid[s8, 1].any() and valid[s9, 1, :2].all()
+        assert not valid[s7, 2].any() and not valid[s8, 2].any() and not valid[:, :, 2].any()
+        td = lambda s, e, i: np.float32((float(c["rew"][s, e, i]) + c["gamma"] * float(c["values"][(s + 1) % L, e, i]))
+                                        - float(c["values"][s, e, i]))
+        assert adv[s8, 0, 0] == td(s8, 0, 0) and adv[s9, 1, 0] == td(s9, 1, 0) and adv[s8, 3, 1] == td(s8, 3, 1)
+        assert adv[s7, 3, 1] != td(s7, 3, 1) and adv[s8, 7, 0] != td(s8, 7, 0)    # an uncut row is more than its TD error
+    # count = steps: the events before step 0 are not planted, the others are where they were
+    c = gae_layouts.row_groups(9, False)
+    assert c["count"] == 9 and c["skip"][1, 0] and c["skip"][0, 1] and c["skip"][[0, 1], 2].all() and c["ended"][0, 3]
+    assert c["skip"][2, 7] and int(c["skip"][:, :8].sum()) == 5
+    assert not c["done"][:, :4].any() and c["done"][0, 6, 0] and int(c["done"][:, :8].sum()) == 1
+    c = gae_layouts.row_groups(7, False)
+    assert c["skip"][0, 7] and int(c["skip"][:, :8].sum()) == 1 and not c["ended"][:, :8].any() and not c["done"][:, :8].any()
+
+
+@pytest.mark.parametrize("shape", [(16385, 4, 257), (43691, 3, 513)], ids=["257_partials", "513_partials"])
+def test_summation_order_equals_the_loop_past_256_partials(shape):
+    """The geometry of the two largest GPU cases, reduced to one step and a few hundred valid entries: thread t of the last
+    sum adds partials t, t + 256 (and t + 512); the last workgroup holds 4 columns (1 column)."""
+    E, N, blocks = shape
+    cols = E * N
+    assert -(-cols // gae_ref.BLOCK) == blocks > gae_ref.BLOCK
+    rng = np.random.default_rng(blocks)
+    adv = np.zeros((2, E, N), np.float32)
+    valid = np.zeros((2, E, N), np.uint8)
+    pick = np.unique(np.concatenate([rng.choice(cols, 600, replace=False),
+                                     [0, 255, 256, 256 * 256, 256 * 256 + 1, 512 * 256 if blocks > 512 else 0, cols - 1]]))
+    valid[0].reshape(-1)[pick] = 1
+    adv[0].reshape(-1)[pick] = (rng.normal(size=pick.size) * 10.0 ** rng.integers(-3, 4, pick.size)).astype(np.float32)
+    adv[1] = 9.0                                                              # outside the window
+    touched = {int(q) // gae_ref.BLOCK for q in pick}
+    assert {0, 256, blocks - 1} <= touched and any(b % 256 == b2 % 256 and b != b2 for b in touched for b2 in touched)
+    st, st2 = gae_ref.stats(adv, valid, 1, 1), gae_ref.stats_loop(adv, valid, 1, 1)
+    assert st[0] == st2[0] == pick.size and same(np.float64(st[1:]), np.float64(st2[1:])), (st, st2)
+    want = adv[0][valid[0] == 1].astype(np.float64)
+    assert abs(st[1] - want.mean()) <= pick.size * 2.0 ** -52 * np.abs(want).mean()
+    assert abs(st[2] - np.std(want, ddof=1)) <= pick.size * 2.0 ** -52 * np.std(want, ddof=1)
+
+
+# ---- the definition itself ---------------------------------------------------------------------------------------------------
+
+def _against_the_definition(case):
+    """gae_ref.gae's adv and ret against the forward view in exact arithmetic:
+        |got − exact| <= 2^-24·|exact| + steps·2^-50·M + 2^-149
+    One float32 rounding of the result; at most eight float64 roundings per row of the recurrence (the casts are exact; γ·V, r
+    + b, − V, γλ·A⁺, + δ, and for ret + V; γλ itself is one rounded product), each at most 2^-53 of a quantity bounded by M,
+    the same sum over absolute values, accumulated over at most `steps` rows: steps · 8 · 2^-53 · M; the subnormal floor."""
+    import gae_forward
+    from fractions import Fraction
+    kw = gae_layouts.ref_args(case)
+    adv, ret, valid = gae_ref.gae(**kw)
+    exact = gae_forward.forward_view(**kw)
+    L, steps = case["T"] + 1, case["steps"]
+    sk, _ = gae_ref.flag_rows(case["done"], case["skip"], case["ended"])
+    slots = gae_ref.window_slots(case["count"], steps, L)
+    assert not valid[slots][sk[slots]].any()                                  # skip rows are not entries
+    keys = {(k, e, i) for k in range(case["count"] - steps, case["count"]) for e in range(case["E"]) for i in range(case["N"])
+            if valid[k % L, e, i]}
+    assert keys == set(exact) and len(keys) > 0
+    worst, lengths = 0.0, set()
+    for (k, e, i), (A, R, M, MR) in exact.items():
+        for got, want, scale in ((adv[k % L, e, i], A, M), (ret[k % L, e, i], R, MR)):
+            bound = Fraction(1, 2 ** 24) * abs(want) + steps * Fraction(1, 2 ** 50) * scale + Fraction(1, 2 ** 149)
+            err = abs(Fraction(float(got)) - want)
+            worst = max(worst, float(err / bound))
+            assert err <= bound, (k, e, i, float(got), float(want), float(err), float(bound))
+    return worst, len(keys)
+
+
+@pytest.mark.parametrize("name", ["seed1", "seed2", "seed3", "gamma1_lambda1", "one_learner", "packed"])
+def test_restatement_against_the_definition_in_exact_arithmetic(name):
+    kw = dict(T=20, count=33, steps=20, gamma=0.99, lam=0.95)
+    case = {"seed1": lambda: gae_layouts._base(4, 2, seed=91, **kw),
+            "seed2": lambda: gae_layouts._base(4, 2, seed=92, **kw),
+            "seed3": lambda: gae_layouts._base(4, 2, seed=93, **kw),
+            "gamma1_lambda1": lambda: gae_layouts._base(4, 2, seed=94, **dict(kw, gamma=1.0, lam=1.0)),
+            "one_learner": lambda: gae_layouts._base(4, 2, seed=95, learners=1, **kw),
+            "packed": lambda: gae_layouts.packed(gae_layouts._base(4, 2, seed=96, **kw))}[name]()
+    flags = gae_ref.flag_rows(case["done"], case["skip"], case["ended"])
+    assert (case["done"] & 1).any() and flags[0].any() and flags[1].any()
+    worst, n = _against_the_definition(case)
+    print(f"{name}: {n} entries, worst |got - exact| / bound = {worst:.3f}")
+
+
+def test_the_definition_sees_a_wrong_recurrence():
+    """The forward view has teeth: a restatement that bootstrapped through an agent's done, or let the carry pass a skip row,
+    would miss the bound by orders of magnitude."""
+    import gae_forward
+    from fractions import Fraction
+    case = gae_layouts._base(4, 2, T=20, count=33, steps=20, seed=91)
+    kw = gae_layouts.ref_args(case)
+    adv, ret, valid = gae_ref.gae(**kw)
+    exact = gae_forward.forward_view(**kw)
+    for wrong in (dict(kw, done=np.zeros_like(case["done"])), dict(kw, skip=np.zeros_like(case["skip"]))):
+        bad, _, _ = gae_ref.gae(**wrong)
+        off = [abs(Fraction(float(bad[k % 21, e, i])) - A) / (Fraction(1, 2 ** 24) * abs(A) + 20 * Fraction(1, 2 ** 50) * M)
+               for (k, e, i), (A, _, M, _) in exact.items() if abs(A) > 0]
+        assert max(off) > 1e4
 
 
 # ---- the library -----------------------------------------------------------------------------------------------------------

@@ -2,7 +2,10 @@
 stats record bit-identical to tests/gae_ref.py -- on every crafted layout in both flag layouts, at shapes of one partly filled
 wavefront, several wavefronts with a ragged last workgroup and several workgroups, and on a ring written by real env steps
 with resets, truncations and the wrap; rows outside the window untouched; two calls the same bytes; a call on a side stream.
-A NaN matches any NaN (the header leaves its payload open)."""
+Further: windows of 7, 8, 9, 15, 16, 17, 23 and 24 steps on a ring of T = 24 with events planted on the rows either side of
+the walk's groups of eight rows, wrapped and from the ring's step 0; 1, 3, 5 and 7 agents per env at 280-300 columns, so that
+an env's columns lie in two wavefronts and in two workgroups; 257 and 513 workgroups, where the last sum adds two and three
+partials per thread.  A NaN matches any NaN (the header leaves its payload open)."""
 import numpy as np
 import pytest
 import torch
@@ -69,6 +72,46 @@ def test_every_layout_at_the_other_small_shapes(name, shape):
 def test_several_wavefronts_and_workgroups(shape, packed_flags):
     E, N, T, learners = shape
     _run_case(gae_layouts.big(E, N, T, learners=learners), packed_flags)
+
+
+@pytest.mark.parametrize("packed_flags", [False, True], ids=["rows", "packed"])
+@pytest.mark.parametrize("wrapped", [True, False], ids=["count40", "count_steps"])
+@pytest.mark.parametrize("steps", gae_layouts.GROUP_STEPS)
+def test_windows_around_the_row_groups(steps, wrapped, packed_flags):
+    """100 x 3, two learners, T = 24: windows of 7 ... 24 steps -- a full group of fetched rows followed by a ragged one, two
+    and three groups -- with a skip, an ended, a done and a parked agent on the rows either side of a group boundary."""
+    case = gae_layouts.row_groups(steps, wrapped)
+    assert case["steps"] == steps and case["count"] == (40 if wrapped else steps)
+    assert (case["E"], case["N"], case["learners"], case["T"]) == (100, 3, 2, 24)
+    _run_case(case, packed_flags)
+
+
+def _straddles(E, N, width):
+    """Envs whose N columns e·N ... e·N + N − 1 lie in two different runs of `width` columns."""
+    return [e for e in range(E) if (e * N) // width != (e * N + N - 1) // width]
+
+
+@pytest.mark.parametrize("packed_flags", [False, True], ids=["rows", "packed"])
+@pytest.mark.parametrize("shape", [(300, 1, None), (100, 3, None), (60, 5, 3), (40, 7, 1)], ids=["300x1", "100x3", "60x5_l3", "40x7_l1"])
+def test_envs_across_wavefront_and_workgroup_edges(shape, packed_flags):
+    """Agent counts that do not divide 64: an env's columns lie in two wavefronts, and in two workgroups, so col / agents,
+    col % agents and the packed-flag read from agent 0's byte cross both edges.  300 x 1 is agents = 1."""
+    E, N, learners = shape
+    assert E * N > gae_ref.BLOCK
+    if N > 1:
+        assert _straddles(E, N, gae_ref.WAVE) and _straddles(E, N, gae_ref.BLOCK), (E, N)
+    case = gae_layouts.big(E, N, 12, learners=learners, seed=73)
+    assert case["count"] > case["T"] + 1 and case["steps"] == 12              # the window wraps
+    _run_case(case, packed_flags)
+
+
+@pytest.mark.parametrize("shape", [(16385, 4, 2, 257, 4, False), (43691, 3, 3, 513, 1, True)], ids=["257_workgroups", "513_workgroups"])
+def test_more_workgroups_than_one_workgroup_has_threads(shape):
+    """total() adds two and three partials per thread; the last workgroup holds 4 columns and 1 column."""
+    E, N, T, blocks, last, packed_flags = shape
+    assert -(-E * N // gae_ref.BLOCK) == blocks and E * N - (blocks - 1) * gae_ref.BLOCK == last
+    ra, out = _run_case(gae_layouts.big(E, N, T, seed=74), packed_flags)
+    assert int(ra.stats.n) > 256 * gae_ref.BLOCK
 
 
 def test_without_normalisation_the_walk_alone_runs():
