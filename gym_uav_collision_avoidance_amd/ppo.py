@@ -18,7 +18,12 @@ the regime where torch's GEMMs are the right tool (README, large-batch figures),
 Nothing in update() reads the device from the host, so the set of rows cannot shrink to the valid ones: every (step, env,
 learner) row of the window is a row of the batch, and a 0/1 weight takes out what is not a sample -- re-initialisation rows
 (valid = 0) and rows of an agent that was already done before the step (parked in an env that went on: the previous row's
-done, unless that row ended the episode or was a re-initialisation).  Every mean below is Σ w·x / max(1, Σ w)."""
+done, unless that row ended the episode or was a re-initialisation).  Every mean below is Σ w·x / max(1, Σ w).
+
+fused_heads=True keeps the GEMMs, autograd through the two networks, the clip and Adam in torch and runs what lies between
+them in HIP (ppo_heads.PPOHeads, libuavx_ppo.so): act() is the policy's forward, the same torch.randn call and
+ONE launch into the slot's u, log π and action; a minibatch is the two forwards, TWO launches that leave the losses and their
+gradient with respect to (μ, log σ, V), and torch.autograd.backward from those three."""
 import math
 
 import torch
@@ -48,10 +53,13 @@ def _positive(name, x, integer=False):
 
 class PPO:
     def __init__(self, mem, generator=None, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5,
-                 ent_coef=0.0, max_grad_norm=0.5, rollout=None):
+                 ent_coef=0.0, max_grad_norm=0.5, rollout=None, fused_heads=False):
         """mem: the DeviceReplay the rollout is collected in (its horizon bounds the rollout; num_learners is respected).
         generator: a torch.Generator on the ring's device for the action noise and the minibatch permutations.
-        rollout: steps per update, default the ring's horizon.  max_grad_norm: None = no clipping."""
+        rollout: steps per update, default the ring's horizon.  max_grad_norm: None = no clipping.
+        fused_heads: sample and evaluate the losses in HIP (module docstring); not part of state_dict()."""
+        if not isinstance(fused_heads, bool):
+            raise ValueError(f"uavx: PPO: fused_heads must be a bool, got {fused_heads!r}")
         _positive("lr", lr), _positive("clip", clip)
         self.epochs, self.minibatches = _positive("epochs", epochs, True), _positive("minibatches", minibatches, True)
         for name, x in (("vf_coef", vf_coef), ("ent_coef", ent_coef)):
@@ -80,6 +88,10 @@ class PPO:
         self.values = None            # what the last update() gave RolloutAdvantages
         self.first_ratio = None       # π / π_old over the first minibatch of the last update()'s first epoch
         self.weight = None            # the 0/1 weight of the last update()'s rows, (step oldest first, env, learner) order
+        self.fused_heads, self.heads = fused_heads, None
+        if fused_heads:
+            from .ppo_heads import PPOHeads
+            self.heads = PPOHeads(dev)
 
     # -- acting --------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -90,6 +102,10 @@ class PPO:
         s = mem.count % mem.L
         mean, log_std = self.policy(mem.state)
         eps = torch.randn(mean.shape, generator=self.generator, device=mean.device, dtype=mean.dtype)
+        if self.fused_heads:
+            out = mem.action_slot()
+            self.heads.sample(mean, log_std, eps, self.u[s], self.logp[s], out)
+            return out
         u = mean + log_std.exp() * eps
         self.u[s].copy_(u)
         self.logp[s].copy_(log_prob(mean, log_std, u))
@@ -137,6 +153,25 @@ class PPO:
             log = {"policy_loss": [], "value_loss": [], "entropy": []}
             for j in range(self.minibatches):
                 idx = perm[j * size:(j + 1) * size]
+                if self.fused_heads:
+                    x = obs[idx]
+                    mean, log_std = self.policy(x)
+                    v = self.value(x).squeeze(-1)
+                    with torch.no_grad():
+                        out = self.heads.loss(mean.detach(), log_std.detach(), v.detach(), idx, u, logp_old, adv, ret, weight,
+                                              self.clip, self.vf_coef, self.ent_coef)
+                    self.optimizer.zero_grad(set_to_none=True)
+                    torch.autograd.backward([mean, log_std, v], [out.g_mean, out.g_log_std, out.g_v])
+                    if self.max_grad_norm is not None:
+                        torch.nn.utils.clip_grad_norm_(self.params, self.max_grad_norm)
+                    self.optimizer.step()
+                    if epoch == 0 and j == 0:
+                        self.first_ratio = out.ratio.clone()
+                    if epoch == self.epochs - 1:          # out's views are overwritten by the next minibatch
+                        log["policy_loss"].append(out.policy_loss.clone())
+                        log["value_loss"].append(out.value_loss.clone())
+                        log["entropy"].append(out.entropy.clone())
+                    continue
                 w = weight[idx]
                 denom = w.sum().clamp(min=1.0)
                 mean, log_std = self.policy(obs[idx])
