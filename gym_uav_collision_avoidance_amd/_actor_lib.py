@@ -1,20 +1,12 @@
-"""ctypes binding of libuavx_actor.so: the fused actor, critic, TD-target, gradient, optimiser, replay, learner-tail and
-exploration kernels.  UNITS describes its eleven units once -- header, bound ABI version, every exported function with its
-restype and argtypes -- and load(), _sources() and the *_HEADER, *_SYMBOLS and *_ABI_VERSION names all come from that table.
-Built, checked for staleness and loaded like libuavx.so (_lib.py), from a directory of its own so that the environment
-library and the source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device
-raises."""
-import collections
+"""libuavx_actor.so: the fused actor, critic, TD-target, gradient, optimiser, replay, learner-tail and exploration kernels,
+declared once.  UNITS describes its eleven units -- header, bound ABI version, every exported function with its restype and
+argtypes -- and LIB = _native.Library(...) over them is everything else: sources, hash, build, staleness, load and bind.  The
+module's other names are aliases of that object and of the table.  Its directory is its own, so that the environment library
+and the source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device raises."""
 import ctypes
-import glob
-import os
 
 from . import _native
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-CSRC = os.path.join(_HERE, "actor_csrc")
-LIB_PATH = os.path.join(CSRC, "libuavx_actor.so")
+from ._native import Unit, unit as _unit  # noqa: F401
 
 SAC, TD3, DDPG = 0, 1, 2
 F32, BF16 = 0, 1
@@ -35,8 +27,6 @@ EXPLORE_STATE_BYTES = 16        # UAVX_EXPLORE_STATE_BYTES
 NSTEP_MAX = 8                   # UAVX_NSTEP_MAX
 NSTEP_MAX_ROWS = 1048576        # UAVX_NSTEP_MAX_ROWS
 NSTEP_SINGLE_ROWS = 1024        # UAVX_NSTEP_SINGLE_ROWS: up to here one launch and no workspace
-
-_lib_handle = None
 
 
 class ReplayRing(ctypes.Structure):
@@ -71,16 +61,6 @@ class ExploreArgs(ctypes.Structure):
 _vp, _i64, _i32, _f32, _f64, _str = (ctypes.c_void_p, ctypes.c_int64, ctypes.c_int, ctypes.c_float, ctypes.c_double,
                                  ctypes.c_char_p)
 _pvp, _pi64 = ctypes.POINTER(_vp), ctypes.POINTER(_i64)
-
-# word: the unit's name in the ABI-mismatch message; version: the function that returns the ABI version the library speaks;
-# abi: the version this package binds; functions: every symbol the header declares (tests check the built library exports
-# each of them) -> (restype, argtypes)
-Unit = collections.namedtuple("Unit", "word header version abi functions")
-
-
-def _unit(word, header, abi, functions):
-    return Unit(word, os.path.join(_INCLUDE, header), next(iter(functions)), abi, functions)
-
 
 UNITS = (
     _unit("actor", "uavx_actor.h", 1, {
@@ -148,44 +128,10 @@ UNITS = (
  POLICY_GRAD_ABI_VERSION, LEARNER_ABI_VERSION, EXPLORE_ABI_VERSION, NSTEP_ABI_VERSION,
  WGRAD_ABI_VERSION) = (u.abi for u in UNITS)
 
-
-def _sources():
-    return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-            + [u.header for u in UNITS])
-
-
-def source_hash():
-    """sha256 over the code (comments and whitespace dropped) of actor_csrc/*.hip, *.hpp and the eleven headers of include/, plus
-    the Makefile without comments and any HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
-    return _native.source_hash(CSRC, _sources())
-
-
-def build(force=False):
-    """hipcc build of actor_csrc/ into libuavx_actor.so (gfx950), under a file lock and renamed into place (_native.build)."""
-    return _native.build(CSRC, LIB_PATH, source_hash, _up_to_date, force)
-
-
-def _up_to_date():
-    """Does LIB_PATH carry the hash of the sources in the tree (read from the file, not through dlopen)?"""
-    return _native.up_to_date(CSRC, LIB_PATH, b"UAVX_ACTOR_SRC_HASH", _sources(), source_hash)
-
-
-def load():
-    global _lib_handle
-    if _lib_handle is not None:
-        return _lib_handle
-    if not os.path.exists(LIB_PATH) or not _up_to_date():
-        build()                 # a build, not a fallback: a compile error is raised as such
-    L = ctypes.CDLL(LIB_PATH)
-    for u in UNITS:
-        for name, (restype, argtypes) in u.functions.items():       # the version function comes first
-            f = getattr(L, name)
-            f.restype, f.argtypes = restype, argtypes
-            if name == u.version and f() != u.abi:
-                raise RuntimeError(f"{LIB_PATH} speaks {u.word} ABI version {f()}, this package binds {u.abi}: "
-                                   f"rebuild it (`make -B -C {CSRC}`)")
-    _lib_handle = L
-    return L
+LIB = _native.Library("actor_csrc", "libuavx_actor.so", b"UAVX_ACTOR_SRC_HASH", UNITS)
+CSRC, LIB_PATH = LIB.csrc, LIB.path
+load, loaded, build, source_hash, _sources, _up_to_date = (LIB.load, LIB.loaded, LIB.build, LIB.source_hash, LIB.sources,
+                                                           LIB.up_to_date)
 
 
 def check(rc, what):
@@ -198,10 +144,5 @@ def check_critic(rc, what):
         raise RuntimeError(f"uavx: {what} failed: {load().uavx_critic_strerror(rc).decode()} ({rc})")
 
 
-_WGRAD_ERRORS = {ERR_INVALID_ARG: "invalid argument", ERR_HIP: "HIP error", ERR_UNSUPPORTED: "unsupported"}
-
-
-def check_wgrad(rc, what):
-    """uavx_wcritic_grad.h has no strerror of its own, and uavx_critic_strerror words two of its three codes otherwise."""
-    if rc != OK:
-        raise RuntimeError(f"uavx: {what} failed: {_WGRAD_ERRORS.get(rc, 'unknown error')} ({rc})")
+# uavx_wcritic_grad.h has no strerror of its own, and uavx_critic_strerror words two of its three codes otherwise
+check_wgrad = LIB.check

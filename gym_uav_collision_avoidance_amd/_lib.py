@@ -211,10 +211,6 @@ def load():
     L.uavx_uw_step_ex.argtypes = [vp, ctypes.POINTER(UWStepArgs), vp]
     L.uavx_uw_get_episode_stats.argtypes = [vp, vp, vp, vp]
     L.uavx_uw_clear_episode_stats.argtypes = [vp, vp]
-    for name in SYMBOLS:
-        fn = getattr(L, name)
-        if fn.restype is ctypes.c_int and name not in ("uavx_version",):
-            fn.restype = i32
     _lib = L
     return L
 

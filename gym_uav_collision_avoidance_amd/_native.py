@@ -1,8 +1,16 @@
-"""What the two ctypes loaders (_lib.py: libuavx.so, _actor_lib.py: libuavx_actor.so) do alike: the identity of a library's
-sources, the hipcc build of one source directory and the staleness check of a built library.  Each function takes the
-directory, the source list, the library path and the marker name of the library it is asked about."""
+"""What every ctypes loader of the package does alike.  The free functions are the mechanics -- the identity of a library's
+sources (source_hash), the hipcc build of one source directory (build) and the staleness check of a built library
+(up_to_date) -- and each takes the directory, the source list, the library path and the marker name of the library it is
+asked about; _lib.py (libuavx.so), whose path is decided at run time, calls them directly.  Library is the whole life of one
+of the other libraries on top of them: described once by its directory, file, marker and Units, it lists its sources, builds,
+checks staleness, loads, binds and words its status codes."""
+import collections
+import ctypes
 import os
 import subprocess
+
+PACKAGE = os.path.dirname(os.path.abspath(__file__))
+INCLUDE = os.path.join(os.path.dirname(PACKAGE), "include")
 
 
 def code_only(text):
@@ -111,3 +119,73 @@ def up_to_date(csrc, lib_path, marker, sources, srchash):
     if mark.group(1):
         return mark.group(1).decode() == srchash()
     return os.path.getmtime(lib_path) >= max(os.path.getmtime(f) for f in sources + [os.path.join(csrc, "Makefile")])
+
+
+# word: the unit's name in the ABI-mismatch message; header: its file under include/; version: the function that returns the
+# ABI version the library speaks; abi: the version this package binds; functions: every symbol the header declares (tests
+# check the built library exports each of them) -> (restype, argtypes)
+Unit = collections.namedtuple("Unit", "word header version abi functions")
+
+
+def unit(word, header, abi, functions):
+    """The Unit of include/`header`; its version function is the first of `functions`."""
+    return Unit(word, os.path.join(INCLUDE, header), next(iter(functions)), abi, functions)
+
+
+class Library:
+    """One native library, from its sources to a bound handle.  csrc: its source directory (a name under the package
+    directory, or a path), file: the library's name in it, marker: the name its embedded source hash stands behind, units: its
+    Units, extras: the headers of include/ that the sources include but no unit owns.  Constructing one touches no file and
+    maps nothing; there is NO fallback: a missing library is built, and a compile error is raised as such."""
+    WORDS = {-1: "invalid argument", -2: "HIP error", -3: "unsupported"}
+
+    def __init__(self, csrc, file, marker, units, extras=()):
+        self.csrc = os.path.join(PACKAGE, csrc)
+        self.path = os.path.join(self.csrc, file)
+        self.marker, self.units = marker, tuple(units)
+        self.extras = [os.path.join(INCLUDE, h) for h in extras]
+        self.handle = None
+
+    def sources(self):
+        """The *.hip and *.hpp of csrc sorted, the unit headers in unit order, the extras: the order enters the hash."""
+        import glob
+        return (sorted(glob.glob(os.path.join(self.csrc, "*.hip")) + glob.glob(os.path.join(self.csrc, "*.hpp")))
+                + [u.header for u in self.units] + self.extras)
+
+    def source_hash(self):
+        """sha256 over the code (comments and whitespace dropped) of sources(), plus the Makefile without comments and any
+        HIPCC / ARCH / HIPFLAGS override (source_hash above); 16 hex digits."""
+        return source_hash(self.csrc, self.sources())
+
+    def build(self, force=False):
+        """hipcc build of csrc into the library (gfx950), under a file lock and renamed into place (build above)."""
+        return build(self.csrc, self.path, self.source_hash, self.up_to_date, force)
+
+    def up_to_date(self):
+        """Does the library carry the hash of the sources in the tree (read from the file, not through dlopen)?"""
+        return up_to_date(self.csrc, self.path, self.marker, self.sources(), self.source_hash)
+
+    def loaded(self):
+        """Has this process mapped the library?"""
+        return self.handle is not None
+
+    def load(self):
+        if self.handle is None:
+            if not os.path.exists(self.path) or not self.up_to_date():
+                self.build()            # a build, not a fallback: a compile error is raised as such
+            L = ctypes.CDLL(self.path)
+            for u in self.units:
+                for name, (restype, argtypes) in u.functions.items():       # the version function comes first
+                    f = getattr(L, name)
+                    f.restype, f.argtypes = restype, argtypes
+                    if name == u.version and f() != u.abi:
+                        raise RuntimeError(f"{self.path} speaks {u.word} ABI version {f()}, this package binds {u.abi}: "
+                                           f"rebuild it (`make -B -C {self.csrc}`)")
+            self.handle = L
+        return self.handle
+
+    def check(self, rc, what):
+        """For the units without a strerror of their own; WORDS has every code their headers name (none answers -4, not
+        packed, which only the actor and critic units do, through their own strerror)."""
+        if rc != 0:
+            raise RuntimeError(f"uavx: {what} failed: {self.WORDS.get(rc, 'unknown error')} ({rc})")

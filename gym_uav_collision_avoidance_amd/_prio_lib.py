@@ -1,20 +1,12 @@
-"""ctypes binding of libuavx_prio.so: the prioritized-replay kernels (include/uavx_prio.h).  Built, checked
-for staleness and loaded like libuavx_actor.so (_actor_lib.py, on _native.py), from a directory of its own so that the actor
-library and the source hash it carries do not change with it.  One unit: its header, the ABI version this package binds and
-every exported function with its restype and argtypes.  There is NO fallback: a missing library or device raises."""
+"""libuavx_prio.so: the prioritized-replay kernels (include/uavx_prio.h), declared once: the constants and
+structures of its header, its one unit -- header, bound ABI version, every exported function with its restype and argtypes
+-- and LIB = _native.Library(...) over it, which is sources, hash, build, staleness, load and bind.  The module's other names
+are aliases of that object and of the table.  Its directory is its own, so that the actor library and the source hash it
+carries do not change with it.  There is NO fallback: a missing library or device raises."""
 import ctypes
-import glob
-import os
 
 from . import _native
 from ._actor_lib import ERR_INVALID_ARG, OK, ReplayRing  # noqa: F401  (the ring and the status codes are uavx_replay.h's)
-
-_HERE = os.path.dirname(os.path.abspath(__file__))
-_INCLUDE = os.path.join(os.path.dirname(_HERE), "include")
-CSRC = os.path.join(_HERE, "prio_csrc")
-LIB_PATH = os.path.join(CSRC, "libuavx_prio.so")
-HEADER = os.path.join(_INCLUDE, "uavx_prio.h")
-ABI_VERSION = 1
 
 ONE = 65536                     # UAVX_PRIO_ONE: Q16.16
 MAX_ENTRIES = 67108864          # UAVX_PRIO_MAX_ENTRIES
@@ -22,8 +14,6 @@ MAX_ROWS = 1048576              # UAVX_PRIO_MAX_ROWS
 MAX_TOWERS = 2                  # UAVX_PRIO_MAX_TOWERS
 FAN = 64                        # children per node of the partial sums
 RECORD_BYTES = 32               # sizeof(uavx_prio_record)
-
-_lib_handle = None
 
 
 class Record(ctypes.Structure):
@@ -61,49 +51,11 @@ FUNCTIONS = {
     "uavx_prio_update": (_i32, [_pstate, _vp, _vp, _i32, _vp, _i64, _i64, _f64, _f64, _vp]),
 }
 SYMBOLS = tuple(FUNCTIONS)
+ABI_VERSION = 1
 
-
-def _sources():
-    return (sorted(glob.glob(os.path.join(CSRC, "*.hip")) + glob.glob(os.path.join(CSRC, "*.hpp")))
-            + [HEADER, os.path.join(_INCLUDE, "uavx_replay.h"), os.path.join(_INCLUDE, "uavx_actor.h")])
-
-
-def source_hash():
-    """sha256 over the code of prio_csrc/*.hip and the three headers it includes, plus the Makefile without comments and any
-    HIPCC / ARCH / HIPFLAGS override (_native.source_hash); 16 hex digits."""
-    return _native.source_hash(CSRC, _sources())
-
-
-def build(force=False):
-    """hipcc build of prio_csrc/ into libuavx_prio.so (gfx950), under a file lock and renamed into place (_native.build)."""
-    return _native.build(CSRC, LIB_PATH, source_hash, _up_to_date, force)
-
-
-def _up_to_date():
-    """Does LIB_PATH carry the hash of the sources in the tree (read from the file, not through dlopen)?"""
-    return _native.up_to_date(CSRC, LIB_PATH, b"UAVX_PRIO_SRC_HASH", _sources(), source_hash)
-
-
-def load():
-    global _lib_handle
-    if _lib_handle is not None:
-        return _lib_handle
-    if not os.path.exists(LIB_PATH) or not _up_to_date():
-        build()                 # a build, not a fallback: a compile error is raised as such
-    L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in FUNCTIONS.items():
-        f = getattr(L, name)
-        f.restype, f.argtypes = restype, argtypes
-    if L.uavx_prio_version() != ABI_VERSION:
-        raise RuntimeError(f"{LIB_PATH} speaks prioritized-replay ABI version {L.uavx_prio_version()}, this package binds "
-                           f"{ABI_VERSION}: rebuild it (`make -B -C {CSRC}`)")
-    _lib_handle = L
-    return L
-
-
-_ERRORS = {-1: "invalid argument", -2: "HIP error", -3: "unsupported", -4: "not packed"}
-
-
-def check(rc, what):
-    if rc != OK:
-        raise RuntimeError(f"uavx: {what} failed: {_ERRORS.get(rc, 'unknown error')} ({rc})")
+LIB = _native.Library("prio_csrc", "libuavx_prio.so", b"UAVX_PRIO_SRC_HASH",
+                      [_native.unit("prioritized-replay", "uavx_prio.h", ABI_VERSION, FUNCTIONS)],
+                      extras=("uavx_replay.h", "uavx_actor.h"))
+CSRC, LIB_PATH, HEADER = LIB.csrc, LIB.path, LIB.units[0].header
+load, loaded, build, source_hash, _sources, _up_to_date, check = (LIB.load, LIB.loaded, LIB.build, LIB.source_hash,
+                                                                  LIB.sources, LIB.up_to_date, LIB.check)
