@@ -4,6 +4,7 @@ rollout buffer the step launch writes into, PPO acts into the ring's action slot
 over the ring in one HIP walk.  The host reads the losses and the episode statistics once per report.
 
     python examples/train_ppo.py [--envs 4096] [--agents 4] [--rollout 32] [--steps 3200] [--fused-heads]
+                                [--normalize-obs] [--normalize-reward]
 """
 import argparse
 import os
@@ -34,6 +35,10 @@ ap.add_argument("--max-grad-norm", type=float, default=0.5)
 ap.add_argument("--report", type=int, default=10, help="updates between reports")
 ap.add_argument("--fused-heads", action="store_true",
                 help="sample and evaluate the losses in HIP between torch's GEMMs (libuavx_ppo.so, DESIGN.md §29)")
+ap.add_argument("--normalize-obs", action="store_true",
+                help="the networks see observations normalised by running statistics (libuavx_norm.so, DESIGN.md §30)")
+ap.add_argument("--normalize-reward", action="store_true",
+                help="GAE reads rewards divided by the running standard deviation of the discounted return (DESIGN.md §30)")
 ap.add_argument("--save-run", type=str, default=None, metavar="FILE",
                 help="write the whole run (worlds, ring, learner, generator, step) to FILE at the end (DESIGN.md §27)")
 ap.add_argument("--resume", type=str, default=None, metavar="FILE",
@@ -50,7 +55,7 @@ mem.begin(venv.reset())
 gen = torch.Generator(device=dev).manual_seed(0)
 agent = PPO(mem, generator=gen, lr=args.lr, gamma=args.gamma, lam=args.lam, clip=args.clip, epochs=args.epochs,
             minibatches=args.minibatches, ent_coef=args.ent_coef, max_grad_norm=args.max_grad_norm,
-            fused_heads=args.fused_heads)
+            fused_heads=args.fused_heads, normalize_obs=args.normalize_obs, normalize_reward=args.normalize_reward)
 
 run = dict(env=venv.env, memory=mem, agent=agent, generator=gen)
 first = 0                      # env steps the run had done when it was saved

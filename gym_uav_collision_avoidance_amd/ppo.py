@@ -23,7 +23,14 @@ done, unless that row ended the episode or was a re-initialisation).  Every mean
 fused_heads=True keeps the GEMMs, autograd through the two networks, the clip and Adam in torch and runs what lies between
 them in HIP (ppo_heads.PPOHeads, libuavx_ppo.so): act() is the policy's forward, the same torch.randn call and
 ONE launch into the slot's u, log π and action; a minibatch is the two forwards, TWO launches that leave the losses and their
-gradient with respect to (μ, log σ, V), and torch.autograd.backward from those three."""
+gradient with respect to (μ, log σ, V), and torch.autograd.backward from those three.
+
+normalize_obs / normalize_reward keep the running statistics of normalize.RolloutNormalizer (libuavx_norm.so):
+the policy and the value net see (obs − mean) / sqrt(var + eps), GAE reads the rewards divided by the standard deviation of
+the discounted return.  update() folds the rollout's returns into the record BEFORE it scales the rewards (the scale is
+defined from the first update on) and the rollout's observations AFTER its last minibatch: the observation record is frozen
+from a rollout's first act() to the end of its update, so the policy that is evaluated is the policy that acted.  Both off
+(the default) is the learner without any of it: the library is not loaded and state_dict() has no "norm"."""
 import math
 
 import torch
@@ -53,13 +60,20 @@ def _positive(name, x, integer=False):
 
 class PPO:
     def __init__(self, mem, generator=None, lr=3e-4, gamma=0.99, lam=0.95, clip=0.2, epochs=4, minibatches=4, vf_coef=0.5,
-                 ent_coef=0.0, max_grad_norm=0.5, rollout=None, fused_heads=False):
+                 ent_coef=0.0, max_grad_norm=0.5, rollout=None, fused_heads=False, normalize_obs=False, normalize_reward=False,
+                 clip_obs=10.0, clip_reward=10.0, norm_eps=1e-8):
         """mem: the DeviceReplay the rollout is collected in (its horizon bounds the rollout; num_learners is respected).
         generator: a torch.Generator on the ring's device for the action noise and the minibatch permutations.
         rollout: steps per update, default the ring's horizon.  max_grad_norm: None = no clipping.
-        fused_heads: sample and evaluate the losses in HIP (module docstring); not part of state_dict()."""
-        if not isinstance(fused_heads, bool):
-            raise ValueError(f"uavx: PPO: fused_heads must be a bool, got {fused_heads!r}")
+        fused_heads: sample and evaluate the losses in HIP (module docstring); not part of state_dict().
+        normalize_obs, normalize_reward: keep running statistics and normalise with them (module docstring); clip_obs,
+        clip_reward, norm_eps: RolloutNormalizer's clip_obs, clip_reward and eps."""
+        for name, x in (("fused_heads", fused_heads), ("normalize_obs", normalize_obs), ("normalize_reward", normalize_reward)):
+            if not isinstance(x, bool):
+                raise ValueError(f"uavx: PPO: {name} must be a bool, got {x!r}")
+        _positive("clip_obs", clip_obs), _positive("clip_reward", clip_reward)
+        if isinstance(norm_eps, bool) or not isinstance(norm_eps, (int, float)) or not math.isfinite(norm_eps) or norm_eps < 0:
+            raise ValueError(f"uavx: PPO: norm_eps must be a finite float >= 0, got {norm_eps!r}")
         _positive("lr", lr), _positive("clip", clip)
         self.epochs, self.minibatches = _positive("epochs", epochs, True), _positive("minibatches", minibatches, True)
         for name, x in (("vf_coef", vf_coef), ("ent_coef", ent_coef)):
@@ -92,6 +106,12 @@ class PPO:
         if fused_heads:
             from .ppo_heads import PPOHeads
             self.heads = PPOHeads(dev)
+        self.normalize_obs, self.normalize_reward, self.norm = normalize_obs, normalize_reward, None
+        if normalize_obs or normalize_reward:
+            from .normalize import RolloutNormalizer
+            self.norm = RolloutNormalizer(mem, gamma=gamma, obs=normalize_obs, reward=normalize_reward, clip_obs=clip_obs,
+                                          clip_reward=clip_reward, eps=norm_eps)
+            self._state = torch.zeros_like(mem.obs[0]) if normalize_obs else None     # what act() shows the policy
 
     # -- acting --------------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -100,7 +120,7 @@ class PPO:
         log π at the slot: call mem.step() next."""
         mem = self.mem
         s = mem.count % mem.L
-        mean, log_std = self.policy(mem.state)
+        mean, log_std = self.policy(self.norm.obs(mem.state, out=self._state) if self.normalize_obs else mem.state)
         eps = torch.randn(mean.shape, generator=self.generator, device=mean.device, dtype=mean.dtype)
         if self.fused_heads:
             out = mem.action_slot()
@@ -115,7 +135,10 @@ class PPO:
 
     @torch.no_grad()
     def select_action(self, obs, evaluate=True):
-        """obs [..., 10] -> actions [..., 2] in [-1, 1] without touching the ring (evaluate.py's policy_fn)."""
+        """obs [..., 10] -> actions [..., 2] in [-1, 1] without touching the ring (evaluate.py's policy_fn).  With
+        normalize_obs the policy sees the observations normalised by the record as it stands."""
+        if self.normalize_obs:
+            obs = self.norm.obs(obs.contiguous())
         return self.policy.act(obs, evaluate=evaluate, generator=self.generator)
 
     # -- learning ------------------------------------------------------------------------------------------------------------
@@ -134,12 +157,15 @@ class PPO:
         device tensors (means over the last epoch's minibatches); nothing is read on the host."""
         mem, nl = self.mem, self.mem.num_learners
         steps = min(self.rollout, mem.count, mem.T)
+        if self.normalize_reward:
+            self.norm.fold_returns()      # before the rewards are scaled: the scale is defined from the first update on
+        ring_obs = self.norm.obs_ring() if self.normalize_obs else mem.obs
         with torch.no_grad():
-            self.values = self.value(mem.obs).squeeze(-1).contiguous()
-        out = self.advantages.compute(self.values, steps)
+            self.values = self.value(ring_obs).squeeze(-1).contiguous()
+        out = self.advantages.compute(self.values, steps, rewards=self.norm.rewards() if self.normalize_reward else None)
         slots = self.advantages.window(steps)
         take = lambda t: t[slots][:, :, :nl]
-        obs = take(mem.obs).reshape(-1, mem.obs.shape[-1])
+        obs = take(ring_obs).reshape(-1, mem.obs.shape[-1])
         u = take(self.u).reshape(-1, 2)
         logp_old = take(self.logp).reshape(-1)
         adv = take(out.adv_norm).reshape(-1)
@@ -194,17 +220,22 @@ class PPO:
                 log["policy_loss"].append(policy_loss.detach())
                 log["value_loss"].append(value_loss.detach())
                 log["entropy"].append(entropy.detach())
+        if self.normalize_obs:
+            self.norm.fold_obs()          # after the last minibatch: the record was frozen while the rollout was evaluated
         self.updates += 1
         return {k: torch.stack(v).mean() for k, v in log.items()}
 
     # -- snapshot / restore (checkpoint.py) ---------------------------------------------------------------------
     def state_dict(self, include_sampler=True):
         """Tensors and built-in types only: the two networks, Adam's state, the per-slot u and log π (left out with
-        include_sampler=False, as the ring then is), the update count."""
+        include_sampler=False, as the ring then is), the update count; with normalize_obs or normalize_reward also "norm",
+        the normalizer's record, carry and counters."""
         sd = {"kind": "ppo", "policy": dict(self.policy.state_dict()), "value": dict(self.value.state_dict()),
               "optimizer": self.optimizer.state_dict(), "updates": int(self.updates)}
         if include_sampler:
             sd["u"], sd["logp"] = self.u, self.logp
+        if self.norm is not None:
+            sd["norm"] = self.norm.state_dict()
         return sd
 
     def load_state_dict(self, sd):
@@ -215,12 +246,19 @@ class PPO:
             if name in sd and (not torch.is_tensor(sd[name]) or tuple(sd[name].shape) != tuple(getattr(self, name).shape)
                                or sd[name].dtype != torch.float32):
                 raise ValueError(f"uavx: the saved PPO's {name!r} does not fit this ring")
+        if ("norm" in sd) != (self.norm is not None):
+            raise ValueError("uavx: the saved PPO was trained %s normalisation, this one is built %s it"
+                             % (("with", "without") if "norm" in sd else ("without", "with")))
+        if self.norm is not None:
+            self.norm.check_state(sd["norm"])
         self.policy.load_state_dict(sd["policy"])
         self.value.load_state_dict(sd["value"])
         self.optimizer.load_state_dict(sd["optimizer"])
         for name in ("u", "logp"):
             if name in sd:
                 getattr(self, name).copy_(sd[name])
+        if self.norm is not None:
+            self.norm.load_state_dict(sd["norm"])
         self.updates = int(sd["updates"])
         return self
 

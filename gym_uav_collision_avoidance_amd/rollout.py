@@ -36,7 +36,7 @@ class RolloutAdvantages:
                                torch.zeros(self.shape, dtype=torch.float32, device=dev) if self.normalize else None)
         self._record = torch.zeros(3, dtype=torch.float64, device=dev)       # uavx_gae_stats: int64 n, double mean, std
         self.stats = Stats(self._record[:1].view(torch.int64)[0], self._record[1], self._record[2])
-        self._lib = self._ring = self._work = None
+        self._lib = self._ring = self._work = self._other = None
 
     def _steps(self, steps):
         count, T = self.mem.count, self.mem.T
@@ -72,8 +72,18 @@ class RolloutAdvantages:
                        "uavx_gae_workspace_bytes")
         self._work = torch.zeros(max(1, need.value // 8), dtype=torch.float64, device=mem.rew.device)
 
-    def compute(self, values, steps=None):
+    def _ring_with(self, rewards):
+        """The ring struct with `rewards` in place of mem.rew (kept: the same tensor comes again every update)."""
+        if self._other is None or self._other.rew != rewards.data_ptr():
+            r = self._ring
+            self._other = self._gae.Ring(rew=rewards.data_ptr(), done=r.done, skip=r.skip, ended=r.ended, slots=r.slots,
+                                         envs=r.envs, agents=r.agents, learners=r.learners)
+        return self._other
+
+    def compute(self, values, steps=None, rewards=None):
         """values: contiguous [L, E, N] float32 device tensor, the caller's V of the observation in every slot of the ring.
+        rewards: None, or a contiguous [L, E, N] float32 tensor on the ring's device that is read in place of mem.rew
+        (normalize.RolloutNormalizer.rewards()).
         Returns Advantages(adv, ret, valid, adv_norm): preallocated [L, E, N] tensors written in the window's rows only
         (window(steps) gathers them), valid until the next call; adv_norm is None without normalize.  The record (n, mean,
         std as 0-d device tensors) is left in .stats.  Enqueued on the current stream; nothing is read on the host."""
@@ -83,11 +93,18 @@ class RolloutAdvantages:
             raise ValueError(f"uavx: RolloutAdvantages: values must be float32 {self.shape}, got {got}")
         if values.device != self.mem.rew.device or not values.is_contiguous():
             raise ValueError("uavx: RolloutAdvantages: values must be contiguous and on the ring's device")
+        if rewards is not None:
+            if not torch.is_tensor(rewards) or rewards.dtype != torch.float32 or tuple(rewards.shape) != self.shape:
+                got = f"{rewards.dtype} {tuple(rewards.shape)}" if torch.is_tensor(rewards) else type(rewards).__name__
+                raise ValueError(f"uavx: RolloutAdvantages: rewards must be float32 {self.shape}, got {got}")
+            if rewards.device != self.mem.rew.device or not rewards.is_contiguous():
+                raise ValueError("uavx: RolloutAdvantages: rewards must be contiguous and on the ring's device")
         if self._lib is None:
             self._bind()
         o = self.outputs
+        ring = self._ring if rewards is None else self._ring_with(rewards)
         with torch.cuda.device(values.device):
-            rc = self._lib.uavx_gae_compute(ctypes.byref(self._ring), values.data_ptr(), self.mem.count, steps, self.gamma,
+            rc = self._lib.uavx_gae_compute(ctypes.byref(ring), values.data_ptr(), self.mem.count, steps, self.gamma,
                                             self.lam, o.adv.data_ptr(), o.ret.data_ptr(), o.valid.data_ptr(),
                                             o.adv_norm.data_ptr() if self.normalize else None,
                                             self._record.data_ptr(), self._work.data_ptr(), self._work.numel() * 8,
