@@ -1,9 +1,11 @@
 """libuavx_clip.so: the Adam step behind a clip of the norm of all gradients (include/uavx_clip.h), declared
 once: the constants and structures of its header, its one unit -- header, bound ABI version, every exported function with
 its restype and argtypes -- and LIB = _native.Library(...) over it, which is sources, hash, build, staleness, load and bind.
-The module's other names are aliases of that object and of the table.  Its directory is its own, so that the actor library
-and the source hash it carries do not change with it.  Nothing imports this module until a FusedAdam is built with
-max_grad_norm, and importing it neither builds nor maps anything.  There is NO fallback: a missing library or device raises."""
+The module's other names are aliases of that object and of the table.  Its directory is its own; the clip, gae, ppo and norm
+libraries share the headers of common_csrc/, whose code enters the source hash of each of the four, and the env, actor, prio
+and keywalk libraries share nothing with them (the actor library, whose Adam arithmetic this one restates, stays as it is).
+Nothing imports this module until a FusedAdam is built with max_grad_norm, and importing it neither builds nor maps anything.
+There is NO fallback: a missing library or device raises."""
 import ctypes
 
 from . import _native
@@ -40,7 +42,8 @@ SYMBOLS = tuple(FUNCTIONS)
 ABI_VERSION = 1
 
 LIB = _native.Library("clip_csrc", "libuavx_clip.so", b"UAVX_CLIP_SRC_HASH",
-                      [_native.unit("clip", "uavx_clip.h", ABI_VERSION, FUNCTIONS)], extras=("uavx_actor.h",))
+                      [_native.unit("clip", "uavx_clip.h", ABI_VERSION, FUNCTIONS)], extras=("uavx_actor.h",),
+                      shared=("uavx_block_reduce.hpp", "uavx_entry.hpp"))
 CSRC, LIB_PATH, HEADER = LIB.csrc, LIB.path, LIB.units[0].header
 load, loaded, build, source_hash, _sources, _up_to_date, check = (LIB.load, LIB.loaded, LIB.build, LIB.source_hash,
                                                                   LIB.sources, LIB.up_to_date, LIB.check)

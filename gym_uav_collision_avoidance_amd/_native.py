@@ -135,22 +135,24 @@ def unit(word, header, abi, functions):
 class Library:
     """One native library, from its sources to a bound handle.  csrc: its source directory (a name under the package
     directory, or a path), file: the library's name in it, marker: the name its embedded source hash stands behind, units: its
-    Units, extras: the headers of include/ that the sources include but no unit owns.  Constructing one touches no file and
-    maps nothing; there is NO fallback: a missing library is built, and a compile error is raised as such."""
+    Units, extras: the headers of include/ that the sources include but no unit owns, shared: the files of common_csrc/ (names
+    in it, or paths) that the sources include.  Constructing one touches no file and maps nothing; there is NO fallback: a missing library is built, and a compile error is raised as such."""
     WORDS = {-1: "invalid argument", -2: "HIP error", -3: "unsupported"}
 
-    def __init__(self, csrc, file, marker, units, extras=()):
+    def __init__(self, csrc, file, marker, units, extras=(), shared=()):
         self.csrc = os.path.join(PACKAGE, csrc)
         self.path = os.path.join(self.csrc, file)
         self.marker, self.units = marker, tuple(units)
         self.extras = [os.path.join(INCLUDE, h) for h in extras]
+        self.shared = [os.path.join(PACKAGE, "common_csrc", h) for h in shared]
         self.handle = None
 
     def sources(self):
-        """The *.hip and *.hpp of csrc sorted, the unit headers in unit order, the extras: the order enters the hash."""
+        """The *.hip and *.hpp of csrc sorted, the unit headers in unit order, the extras, the shared files as given: the
+        order enters the hash."""
         import glob
         return (sorted(glob.glob(os.path.join(self.csrc, "*.hip")) + glob.glob(os.path.join(self.csrc, "*.hpp")))
-                + [u.header for u in self.units] + self.extras)
+                + [u.header for u in self.units] + self.extras + self.shared)
 
     def source_hash(self):
         """sha256 over the code (comments and whitespace dropped) of sources(), plus the Makefile without comments and any

@@ -1,8 +1,9 @@
 """libuavx_ppo.so: PPO's sampling and loss heads (include/uavx_ppo.h), declared once: the constants of its
 header, its one unit -- header, bound ABI version, every exported function with its restype and argtypes -- and
 LIB = _native.Library(...) over it, which is sources, hash, build, staleness, load and bind.  The module's other names are
-aliases of that object and of the table.  Its directory is its own, so that no other library and no source hash changes with
-it.  Nothing imports this module until a PPOHeads launches, and importing it neither builds nor maps anything.  There is NO
+aliases of that object and of the table.  Its directory is its own; the clip, gae, ppo and norm libraries share the headers of
+common_csrc/, whose code enters the source hash of each of the four, and the env, actor, prio and keywalk libraries share
+nothing with them.  Nothing imports this module until a PPOHeads launches, and importing it neither builds nor maps anything.  There is NO
 fallback: a missing library or device raises."""
 import ctypes
 
@@ -27,7 +28,8 @@ SYMBOLS = tuple(FUNCTIONS)
 ABI_VERSION = 1
 
 LIB = _native.Library("ppo_csrc", "libuavx_ppo.so", b"UAVX_PPO_SRC_HASH",
-                      [_native.unit("ppo", "uavx_ppo.h", ABI_VERSION, FUNCTIONS)], extras=("uavx_actor.h",))
+                      [_native.unit("ppo", "uavx_ppo.h", ABI_VERSION, FUNCTIONS)], extras=("uavx_actor.h",),
+                      shared=("uavx_block_reduce.hpp", "uavx_entry.hpp"))
 CSRC, LIB_PATH, HEADER = LIB.csrc, LIB.path, LIB.units[0].header
 load, loaded, build, source_hash, _sources, _up_to_date, check = (LIB.load, LIB.loaded, LIB.build, LIB.source_hash,
                                                                   LIB.sources, LIB.up_to_date, LIB.check)

@@ -17,10 +17,14 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/uavx_clip.h"
+#include "../common_csrc/uavx_block_reduce.hpp"
+#include "../common_csrc/uavx_entry.hpp"
 
 namespace uavx_clip_k {
 
-constexpr int WG = 256, VEC = 4, BLOCK_ELEMS = WG * VEC, MAXT = UAVX_CLIP_MAX_TENSORS, WAVE = 64, WAVES = WG / WAVE;
+using namespace uavx_common;
+
+constexpr int WG = 256, VEC = 4, BLOCK_ELEMS = WG * VEC, MAXT = UAVX_CLIP_MAX_TENSORS, WAVES = WG / WAVE;
 static_assert(BLOCK_ELEMS == UAVX_CLIP_BLOCK, "the header states the block size");
 
 struct Table {
@@ -49,18 +53,6 @@ struct NormTable {
     double *partials;        // this group's part of the workspace
 };
 
-// the sum of a workgroup's values in thread 0: lanes by a shuffle tree, wavefronts through LDS in order
-__device__ inline double block_sum(double s, double *part) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = s;
-    __syncthreads();
-    double r = part[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) r += part[w];
-    return r;
-}
-
 __global__ __launch_bounds__(WG) void sumsq(const NormTable t) {
     __shared__ double part[WAVES];
     const int32_t blk = (int32_t)blockIdx.x;
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(WG) void sumsq(const NormTable t) {
             s += g * g;
         }
     }
-    const double r = block_sum(s, part);
+    const double r = block_sum<WG>(s, part);
     if (threadIdx.x == 0) t.partials[blk] = r;
 }
 
@@ -103,8 +95,8 @@ __global__ __launch_bounds__(WG) void finish(const double *__restrict__ partials
                                              float *scalars, double lr, double beta1, double beta2) {
     __shared__ double part[WAVES];
     double s = 0.0;
-    for (int64_t i = threadIdx.x; i < count; i += WG) s += partials[i];
-    const double S = block_sum(s, part);
+    for (int64_t i = threadIdx.x; i < count; i += WG) s += partials[i];     // total<WG> with a 64-bit count
+    const double S = block_sum<WG>(s, part);
     if (threadIdx.x != 0) return;
     const float norm = (float)sqrt(S);
     const float c = *max_norm / (norm + 1e-6f);
@@ -190,10 +182,6 @@ __global__ __launch_bounds__(WG) void update(const Table t) {
     }
 }
 
-static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
-static bool unit(double x) { return x >= 0.0 && x <= 1.0; }     // false for NaN
-
 // The block numbers of one group; false on a bad count.  Every tensor starts a block of its own.
 static bool plan(int n, const int64_t *numel, int32_t *count, int32_t *first, int64_t &blocks) {
     if (n < 1 || n > MAXT || !numel) return false;
@@ -251,11 +239,7 @@ using namespace uavx_clip_k;
 
 extern "C" {
 
-#ifndef UAVX_CLIP_SRC_HASH
-#define UAVX_CLIP_SRC_HASH ""
-#endif
-// the loader (_clip_lib.py) finds this marker in the file without mapping it
-__attribute__((used)) static const char kBuildInfo[] = "UAVX_CLIP_SRC_HASH=" UAVX_CLIP_SRC_HASH;
+UAVX_BUILD_MARKER(UAVX_CLIP_SRC_HASH);
 
 int uavx_clip_version(void) { return UAVX_CLIP_VERSION; }
 
@@ -290,22 +274,17 @@ int uavx_clip_step(int groups, const uavx_clip_group *g, double *partials, int64
     }
     if (partials_bytes < total * (int64_t)sizeof(double)) return UAVX_ACTOR_ERR_INVALID_ARG;
     const hipStream_t st = (hipStream_t)stream;
-    for (int k = 0; k < groups; ++k) {
-        hipLaunchKernelGGL(sumsq, dim3((unsigned)blocks[k]), dim3(WG), 0, st, norms[k]);
-        if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    }
-    for (int k = 0; k < groups; ++k) {
+    int rc = UAVX_ACTOR_OK;
+    for (int k = 0; k < groups && rc == UAVX_ACTOR_OK; ++k) rc = launch(sumsq, blocks[k], WG, st, norms[k]);
+    for (int k = 0; k < groups && rc == UAVX_ACTOR_OK; ++k) {
         if (k == 0)
-            hipLaunchKernelGGL(finish, dim3(1), dim3(WG), 0, st, (const double *)partials, total, max_norm, rec, g[k].step,
-                               g[k].scalars, g[k].lr, g[k].beta1, g[k].beta2);
+            rc = launch(finish, 1, WG, st, (const double *)partials, total, max_norm, rec, g[k].step, g[k].scalars, g[k].lr,
+                        g[k].beta1, g[k].beta2);
         else
-            hipLaunchKernelGGL(adam_prologue, dim3(1), dim3(64), 0, st, g[k].step, g[k].scalars, g[k].lr, g[k].beta1,
-                               g[k].beta2);
-        if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-        hipLaunchKernelGGL(update, dim3((unsigned)blocks[k]), dim3(WG), 0, st, tabs[k]);
-        if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
+            rc = launch(adam_prologue, 1, 64, st, g[k].step, g[k].scalars, g[k].lr, g[k].beta1, g[k].beta2);
+        if (rc == UAVX_ACTOR_OK) rc = launch(update, blocks[k], WG, st, tabs[k]);
     }
-    return UAVX_ACTOR_OK;
+    return rc;
 }
 
 }  // extern "C"

@@ -17,17 +17,18 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/uavx_gae.h"
+#include "../common_csrc/uavx_block_reduce.hpp"
+#include "../common_csrc/uavx_entry.hpp"
+#include "../common_csrc/uavx_ring_view.hpp"
 
 namespace uavx_gae_k {
 
-constexpr int WG = UAVX_GAE_BLOCK, WAVE = 64, WAVES = WG / WAVE, ROWS = 8;
+using namespace uavx_common;
+
+constexpr int WG = UAVX_GAE_BLOCK, WAVES = WG / WAVE, ROWS = 8;
 static_assert(WG == 256, "the header documents four wavefronts per workgroup");
 
-struct Args {
-    const float *rew;
-    const uint8_t *done;
-    const uint8_t *skip;       // NULL (with ended): flags packed into done
-    const uint8_t *ended;
+struct Args : RingView {
     const float *values;
     float *adv;
     float *ret;
@@ -37,38 +38,11 @@ struct Args {
     double *sum;               // workspace: blocks float64, blocks float64, blocks int64
     double *sq;
     long long *cnt;
-    int64_t plane;             // envs · agents: the elements of one slot
-    int32_t columns;           // = plane
-    int32_t agents, learners;
-    int32_t envs;
-    int32_t slots;
     int32_t first;             // slot of step count − 1
     int32_t boot;              // slot of the state after it: count mod slots
     int32_t steps;
-    int32_t blocks;
     double gamma, gl;          // γ and γ·λ
 };
-
-// the sum of a workgroup's values, in every thread: lanes by a halving tree, wavefronts through LDS left to right
-template <typename T>
-__device__ inline T block_sum(T s, T *part) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = s;
-    __syncthreads();
-    T r = part[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) r += part[w];
-    return r;
-}
-
-// the total of `count` per-workgroup partials, in every thread of the calling workgroup
-template <typename T>
-__device__ inline T total(const T *__restrict__ partial, int count, T *part) {
-    T s = 0;
-    for (int i = threadIdx.x; i < count; i += WG) s += partial[i];
-    return block_sum(s, part);
-}
 
 struct Rows {
     float r[ROWS], v[ROWS];
@@ -84,13 +58,8 @@ __device__ inline void fetch(const Args &a, Rows &b, int32_t &s, int n, int32_t 
             b.r[j] = a.rew[off];
             b.v[j] = a.values[off];
             b.d[j] = a.done[off];
-            if (a.skip) {
-                const int64_t fo = (int64_t)s * a.envs + e;
-                b.f[j] = (a.skip[fo] ? 1u : 0u) | (a.ended[fo] ? 2u : 0u);
-            } else {
-                b.f[j] = ((uint32_t)a.done[(int64_t)s * a.plane + (int64_t)e * a.agents] >> 1) & 3u;
-            }
-            s = s == 0 ? a.slots - 1 : s - 1;
+            b.f[j] = flags(a, s, e);
+            s = prev_slot(a, s);
         }
     }
 }
@@ -98,14 +67,11 @@ __device__ inline void fetch(const Args &a, Rows &b, int32_t &s, int n, int32_t 
 __global__ __launch_bounds__(WG) void walk(const Args a) {
     __shared__ double psum[WAVES];
     __shared__ long long pcnt[WAVES];
-    const int64_t q = (int64_t)blockIdx.x * WG + threadIdx.x;
-    const bool in = q < a.columns;
-    const int32_t col = in ? (int32_t)q : 0;
-    const int32_t e = col / a.agents;
-    const bool learn = in && col - e * a.agents < a.learners;
+    const Column c = column<WG>(a);
+    const int32_t col = c.col, e = c.e;
     double sum = 0.0;
     long long cnt = 0;
-    if (learn) {
+    if (c.learn) {
         Rows cur, nxt{};
         int32_t s = a.first, out = a.first, left = a.steps;
         fetch(a, cur, s, left < ROWS ? left : ROWS, col, e);
@@ -142,24 +108,24 @@ __global__ __launch_bounds__(WG) void walk(const Args a) {
                     a.valid[off] = skip ? 0 : 1;
                     cut = skip;
                     vnext = cur.v[j];
-                    out = out == 0 ? a.slots - 1 : out - 1;
+                    out = prev_slot(a, out);
                 }
             }
             cur = nxt;
         }
-    } else if (in) {
+    } else if (c.in) {
         int32_t out = a.first;
         for (int32_t j = 0; j < a.steps; ++j) {
             const int64_t off = (int64_t)out * a.plane + col;
             a.adv[off] = 0.f;
             a.ret[off] = 0.f;
             a.valid[off] = 0;
-            out = out == 0 ? a.slots - 1 : out - 1;
+            out = prev_slot(a, out);
         }
     }
     if (!a.adv_norm) return;       // uniform over the launch
-    const double S = block_sum(sum, psum);
-    const long long C = block_sum(cnt, pcnt);
+    const double S = block_sum<WG>(sum, psum);
+    const long long C = block_sum<WG>(cnt, pcnt);
     if (threadIdx.x == 0) {
         a.sum[blockIdx.x] = S;
         a.cnt[blockIdx.x] = C;
@@ -169,13 +135,13 @@ __global__ __launch_bounds__(WG) void walk(const Args a) {
 __global__ __launch_bounds__(WG) void spread(const Args a) {
     __shared__ double psum[WAVES], psq[WAVES];
     __shared__ long long pcnt[WAVES];
-    const long long n = total(a.cnt, a.blocks, pcnt);
-    const double S = total(a.sum, a.blocks, psum);
+    const long long n = total<WG>(a.cnt, a.blocks, pcnt);
+    const double S = total<WG>(a.sum, a.blocks, psum);
     const double mean = n > 0 ? S / (double)n : 0.0;
-    const int64_t q = (int64_t)blockIdx.x * WG + threadIdx.x;
-    const int32_t col = (int32_t)q;
+    const Column c = column<WG>(a);
+    const int32_t col = c.col;
     double sq = 0.0;
-    if (q < a.columns && col % a.agents < a.learners) {
+    if (c.learn) {
         const float *__restrict__ adv = a.adv;
         const uint8_t *__restrict__ valid = a.valid;
         int32_t s = a.first;
@@ -189,7 +155,7 @@ __global__ __launch_bounds__(WG) void spread(const Args a) {
                     const int64_t off = (int64_t)s * a.plane + col;
                     x[j] = adv[off];
                     v[j] = valid[off];
-                    s = s == 0 ? a.slots - 1 : s - 1;
+                    s = prev_slot(a, s);
                 }
             }
 #pragma unroll
@@ -201,7 +167,7 @@ __global__ __launch_bounds__(WG) void spread(const Args a) {
             }
         }
     }
-    const double Q = block_sum(sq, psq);
+    const double Q = block_sum<WG>(sq, psq);
     if (threadIdx.x != 0) return;
     a.sq[blockIdx.x] = Q;
     if (blockIdx.x == 0) {
@@ -212,15 +178,15 @@ __global__ __launch_bounds__(WG) void spread(const Args a) {
 
 __global__ __launch_bounds__(WG) void normalise(const Args a) {
     __shared__ double psq[WAVES];
-    const double Q = total(a.sq, a.blocks, psq);
+    const double Q = total<WG>(a.sq, a.blocks, psq);
     const long long n = a.stats->n;
     const double mean = a.stats->mean;
     const double std = n >= 2 ? sqrt(Q / (double)(n - 1)) : 0.0;
     const double denom = std + 1e-8;
     if (blockIdx.x == 0 && threadIdx.x == 0) a.stats->std = std;
-    const int64_t q = (int64_t)blockIdx.x * WG + threadIdx.x;
-    if (q >= a.columns) return;
-    const int32_t col = (int32_t)q;
+    const Column c = column<WG>(a);
+    if (!c.in) return;
+    const int32_t col = c.col;
     const float *__restrict__ adv = a.adv;
     const uint8_t *__restrict__ valid = a.valid;
     float *__restrict__ out = a.adv_norm;
@@ -235,7 +201,7 @@ __global__ __launch_bounds__(WG) void normalise(const Args a) {
                 off[j] = (int64_t)s * a.plane + col;
                 x[j] = adv[off[j]];
                 v[j] = valid[off[j]];
-                s = s == 0 ? a.slots - 1 : s - 1;
+                s = prev_slot(a, s);
             }
         }
 #pragma unroll
@@ -244,35 +210,19 @@ __global__ __launch_bounds__(WG) void normalise(const Args a) {
     }
 }
 
-static bool aligned(const void *p, uintptr_t al) { return ((uintptr_t)p & (al - 1)) == 0; }
-
-static bool unit(double x) { return x >= 0.0 && x <= 1.0; }     // false for NaN
-
-// the number of workgroups of a ring; false on a bad shape
-static bool plan(const uavx_gae_ring *r, int64_t &blocks) {
-    if (!r || r->envs < 1 || r->agents < 1 || r->envs > INT32_MAX || r->agents > INT32_MAX) return false;
-    if (r->envs * r->agents > INT32_MAX) return false;
-    blocks = (r->envs * r->agents + WG - 1) / WG;
-    return true;
-}
-
 }  // namespace uavx_gae_k
 
 using namespace uavx_gae_k;
 
 extern "C" {
 
-#ifndef UAVX_GAE_SRC_HASH
-#define UAVX_GAE_SRC_HASH ""
-#endif
-// the loader (_gae_lib.py) finds this marker in the file without mapping it
-__attribute__((used)) static const char kBuildInfo[] = "UAVX_GAE_SRC_HASH=" UAVX_GAE_SRC_HASH;
+UAVX_BUILD_MARKER(UAVX_GAE_SRC_HASH);
 
 int uavx_gae_version(void) { return UAVX_GAE_VERSION; }
 
 int uavx_gae_workspace_bytes(const uavx_gae_ring *ring, int64_t *bytes) {
     int64_t blocks = 0;
-    if (!bytes || !plan(ring, blocks)) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!bytes || !plan<WG>(ring, blocks)) return UAVX_ACTOR_ERR_INVALID_ARG;
     *bytes = blocks * 24;
     return UAVX_ACTOR_OK;
 }
@@ -280,25 +230,17 @@ int uavx_gae_workspace_bytes(const uavx_gae_ring *ring, int64_t *bytes) {
 int uavx_gae_compute(const uavx_gae_ring *ring, const float *values, int64_t count, int64_t steps, double gamma,
                      double lambda, float *adv, float *ret, uint8_t *valid, float *adv_norm, uavx_gae_stats *stats,
                      void *workspace, int64_t workspace_bytes, void *stream) {
-    int64_t blocks = 0;
-    if (!plan(ring, blocks)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    const uavx_gae_ring &r = *ring;
-    if (r.slots < 2 || r.slots > INT32_MAX || r.learners < 1 || r.learners > r.agents) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!r.rew || !r.done || !values || !adv || !ret || !valid) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if ((r.skip == nullptr) != (r.ended == nullptr)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!aligned(r.rew, 4) || !aligned(values, 4) || !aligned(adv, 4) || !aligned(ret, 4) || !aligned(adv_norm, 4))
+    Args a{};
+    if (!ring_view<WG>(ring, a)) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!a.rew || !values || !adv || !ret || !valid) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!aligned(a.rew, 4) || !aligned(values, 4) || !aligned(adv, 4) || !aligned(ret, 4) || !aligned(adv_norm, 4))
         return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (count < 1 || steps < 1 || steps > count || steps > r.slots - 1) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (count < 1 || steps < 1 || steps > count || steps > a.slots - 1) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (!unit(gamma) || !unit(lambda)) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (adv_norm) {
         if (!stats || !workspace || !aligned(stats, 8) || !aligned(workspace, 8)) return UAVX_ACTOR_ERR_INVALID_ARG;
-        if (workspace_bytes < blocks * 24) return UAVX_ACTOR_ERR_INVALID_ARG;
+        if (workspace_bytes < (int64_t)a.blocks * 24) return UAVX_ACTOR_ERR_INVALID_ARG;
     }
-    Args a{};
-    a.rew = r.rew;
-    a.done = r.done;
-    a.skip = r.skip;
-    a.ended = r.ended;
     a.values = values;
     a.adv = adv;
     a.ret = ret;
@@ -306,29 +248,18 @@ int uavx_gae_compute(const uavx_gae_ring *ring, const float *values, int64_t cou
     a.adv_norm = adv_norm;
     a.stats = stats;
     a.sum = (double *)workspace;
-    a.sq = a.sum + blocks;
-    a.cnt = (long long *)(a.sq + blocks);
-    a.plane = r.envs * r.agents;
-    a.columns = (int32_t)a.plane;
-    a.agents = (int32_t)r.agents;
-    a.learners = (int32_t)r.learners;
-    a.envs = (int32_t)r.envs;
-    a.slots = (int32_t)r.slots;
-    a.first = (int32_t)((count - 1) % r.slots);
-    a.boot = (int32_t)(count % r.slots);
+    a.sq = a.sum + a.blocks;
+    a.cnt = (long long *)(a.sq + a.blocks);
+    a.first = (int32_t)((count - 1) % a.slots);
+    a.boot = (int32_t)(count % a.slots);
     a.steps = (int32_t)steps;
-    a.blocks = (int32_t)blocks;
     a.gamma = gamma;
     a.gl = gamma * lambda;
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(walk, dim3((unsigned)blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    if (!adv_norm) return UAVX_ACTOR_OK;
-    hipLaunchKernelGGL(spread, dim3((unsigned)blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(normalise, dim3((unsigned)blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    return UAVX_ACTOR_OK;
+    int rc = launch(walk, a.blocks, WG, st, a);
+    if (rc == UAVX_ACTOR_OK && adv_norm) rc = launch(spread, a.blocks, WG, st, a);
+    if (rc == UAVX_ACTOR_OK && adv_norm) rc = launch(normalise, a.blocks, WG, st, a);
+    return rc;
 }
 
 }  // extern "C"

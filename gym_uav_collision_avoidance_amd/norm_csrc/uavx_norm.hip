@@ -4,7 +4,7 @@
 //   1. first pass   one thread per column q = e·N + i, adjacent lanes adjacent columns, walking its column's steps oldest to
 //                   newest.  Returns: what a row needs from memory (reward, done byte, the env's flags) does not depend on
 //                   the carry, so the rows are fetched ROWS at a time and the next group is in flight while the recurrence
-//                   runs over this one (uavx_gae.hip's trick; the dependent chain per row is a multiply and an add in
+//                   runs over this one (as uavx_gae.hip's walk; the dependent chain per row is a multiply and an add in
 //                   float64).  Observations: a thread reads the F consecutive floats of its row -- a wavefront's lanes cover
 //                   one contiguous run -- OROWS rows' loads in flight, into F accumulators.  The workgroup leaves sum[f][blk]
 //                   and cnt[blk].
@@ -18,87 +18,36 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/uavx_norm.h"
+#include "../common_csrc/uavx_block_reduce.hpp"
+#include "../common_csrc/uavx_entry.hpp"
+#include "../common_csrc/uavx_ring_view.hpp"
 
 namespace uavx_norm_k {
 
-constexpr int WG = UAVX_NORM_BLOCK, WAVE = 64, WAVES = WG / WAVE, ROWS = 8, OROWS = 4, MAXF = UAVX_NORM_MAX_FEATURES;
+using namespace uavx_common;
+
+constexpr int WG = UAVX_NORM_BLOCK, WAVES = WG / WAVE, ROWS = 8, OROWS = 4, MAXF = UAVX_NORM_MAX_FEATURES;
 static_assert(WG == 256, "the header documents four wavefronts per workgroup");
 
-struct Fold {
-    const float *rew;
-    const uint8_t *done;
-    const uint8_t *skip;       // NULL (with ended): flags packed into done
-    const uint8_t *ended;
+struct Fold : RingView {
     const float *obs;
     double *carry;
     uavx_norm_record *rec;
     double *sum;               // workspace: features × blocks float64, the same again, blocks int64
     double *sq;
     long long *cnt;
-    int64_t plane;             // envs · agents: the elements of one slot
-    int32_t columns;           // = plane
-    int32_t agents, learners;
-    int32_t envs;
-    int32_t slots;
     int32_t start;             // slot of step first
     int32_t prev;              // slot of step first − 1; −1 when first = 0
     int32_t steps;
-    int32_t blocks;
     int32_t features;
     double gamma;
 };
-
-// the sum of a workgroup's values, in every thread: lanes by a halving tree, wavefronts through LDS left to right.  `part`
-// is this call's own: a second call may not reuse it without a barrier in between.
-template <typename T>
-__device__ inline T block_sum(T s, T *part) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = s;
-    __syncthreads();
-    T r = part[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) r += part[w];
-    return r;
-}
-
-// the total of `count` per-workgroup partials, in every thread of the calling workgroup
-template <typename T>
-__device__ inline T total(const T *__restrict__ partial, int count, T *part) {
-    T s = 0;
-    for (int i = threadIdx.x; i < count; i += WG) s += partial[i];
-    return block_sum(s, part);
-}
-
-// bit 0 skip, bit 1 ended of (slot s, env e)
-__device__ inline uint32_t flags(const Fold &a, int32_t s, int32_t e) {
-    if (a.skip) {
-        const int64_t fo = (int64_t)s * a.envs + e;
-        return (a.skip[fo] ? 1u : 0u) | (a.ended[fo] ? 2u : 0u);
-    }
-    return ((uint32_t)a.done[(int64_t)s * a.plane + (int64_t)e * a.agents] >> 1) & 3u;
-}
 
 // does the row before the fold's first park this column's agent in the fold's first row?
 __device__ inline bool parked_at_first(const Fold &a, int32_t col, int32_t e) {
     if (a.prev < 0) return false;
     const uint32_t d = a.done[(int64_t)a.prev * a.plane + col];
     return (d & 1u) && !(flags(a, a.prev, e) & 3u);
-}
-
-struct Column {
-    int32_t col, e;
-    bool learn;
-};
-
-__device__ inline Column column(const Fold &a) {
-    const int64_t q = (int64_t)blockIdx.x * WG + threadIdx.x;
-    const bool in = q < a.columns;
-    Column c;
-    c.col = in ? (int32_t)q : 0;
-    c.e = c.col / a.agents;
-    c.learn = in && c.col - c.e * a.agents < a.learners;
-    return c;
 }
 
 // ---- returns ---------------------------------------------------------------------------------------------------------------
@@ -117,7 +66,7 @@ __device__ inline void fetch(const Fold &a, Rows &b, int32_t &s, int n, int32_t 
             b.r[j] = a.rew[off];
             b.d[j] = a.done[off];
             b.f[j] = flags(a, s, e);
-            s = s + 1 == a.slots ? 0 : s + 1;
+            s = next_slot(a, s);
         }
     }
 }
@@ -163,12 +112,12 @@ __device__ inline double walk(const Fold &a, int32_t col, int32_t e, double mean
 __global__ __launch_bounds__(WG) void ret_sum(const Fold a) {
     __shared__ double psum[WAVES];
     __shared__ long long pcnt[WAVES];
-    const Column c = column(a);
+    const Column c = column<WG>(a);
     double sum = 0.0;
     long long cnt = 0;
     if (c.learn) walk<false>(a, c.col, c.e, 0.0, sum, cnt);
-    const double S = block_sum(sum, psum);
-    const long long N = block_sum(cnt, pcnt);
+    const double S = block_sum<WG>(sum, psum);
+    const long long N = block_sum<WG>(cnt, pcnt);
     if (threadIdx.x == 0) {
         a.sum[blockIdx.x] = S;
         a.cnt[blockIdx.x] = N;
@@ -178,14 +127,14 @@ __global__ __launch_bounds__(WG) void ret_sum(const Fold a) {
 __global__ __launch_bounds__(WG) void ret_sq(const Fold a) {
     __shared__ double psum[WAVES], psq[WAVES];
     __shared__ long long pcnt[WAVES];
-    const long long n = total(a.cnt, a.blocks, pcnt);
-    const double S = total(a.sum, a.blocks, psum);
+    const long long n = total<WG>(a.cnt, a.blocks, pcnt);
+    const double S = total<WG>(a.sum, a.blocks, psum);
     const double mean = n > 0 ? S / (double)n : 0.0;
-    const Column c = column(a);
+    const Column c = column<WG>(a);
     double sq = 0.0;
     long long unused = 0;
     if (c.learn) a.carry[c.col] = walk<true>(a, c.col, c.e, mean, sq, unused);
-    const double Q = block_sum(sq, psq);
+    const double Q = block_sum<WG>(sq, psq);
     if (threadIdx.x == 0) a.sq[blockIdx.x] = Q;
 }
 
@@ -200,16 +149,16 @@ __global__ __launch_bounds__(WG) void obs_pass(const Fold a) {
 #pragma unroll
     for (int f = 0; f < F; ++f) mean[f] = 0.0;
     if (SECOND) {
-        const long long n = total(a.cnt, a.blocks, pcnt);
+        const long long n = total<WG>(a.cnt, a.blocks, pcnt);
         for (int f = 0; f < F; ++f) {
-            const double S = total(a.sum + (int64_t)f * a.blocks, a.blocks, tpart[f]);
+            const double S = total<WG>(a.sum + (int64_t)f * a.blocks, a.blocks, tpart[f]);
             if (threadIdx.x == 0) smean[f] = n > 0 ? S / (double)n : 0.0;
         }
         __syncthreads();
 #pragma unroll
         for (int f = 0; f < F; ++f) mean[f] = smean[f];
     }
-    const Column c = column(a);
+    const Column c = column<WG>(a);
     double acc[F];
 #pragma unroll
     for (int f = 0; f < F; ++f) acc[f] = 0.0;
@@ -232,7 +181,7 @@ __global__ __launch_bounds__(WG) void obs_pass(const Fold a) {
                     const float *__restrict__ row = obs + off * F;
 #pragma unroll
                     for (int f = 0; f < F; ++f) x[j][f] = row[f];
-                    s = s + 1 == a.slots ? 0 : s + 1;
+                    s = next_slot(a, s);
                 }
             }
 #pragma unroll
@@ -256,11 +205,11 @@ __global__ __launch_bounds__(WG) void obs_pass(const Fold a) {
     double *out = SECOND ? a.sq : a.sum;
 #pragma unroll
     for (int f = 0; f < F; ++f) {
-        const double S = block_sum(acc[f], part[f]);
+        const double S = block_sum<WG>(acc[f], part[f]);
         if (threadIdx.x == 0) out[(int64_t)f * a.blocks + blockIdx.x] = S;
     }
     if (!SECOND) {
-        const long long N = block_sum(cnt, pcnt);
+        const long long N = block_sum<WG>(cnt, pcnt);
         if (threadIdx.x == 0) a.cnt[blockIdx.x] = N;
     }
 }
@@ -271,11 +220,11 @@ __global__ __launch_bounds__(WG) void obs_pass(const Fold a) {
 __global__ __launch_bounds__(WG) void merge(const Fold a, const int returns) {
     __shared__ double psum[MAXF][WAVES], psq[MAXF][WAVES];
     __shared__ long long pcnt[WAVES];
-    const long long nb = total(a.cnt, a.blocks, pcnt);
+    const long long nb = total<WG>(a.cnt, a.blocks, pcnt);
     double S = 0.0, Q = 0.0;
     for (int f = 0; f < a.features; ++f) {
-        const double s = total(a.sum + (int64_t)f * a.blocks, a.blocks, psum[f]);
-        const double q = total(a.sq + (int64_t)f * a.blocks, a.blocks, psq[f]);
+        const double s = total<WG>(a.sum + (int64_t)f * a.blocks, a.blocks, psum[f]);
+        const double q = total<WG>(a.sq + (int64_t)f * a.blocks, a.blocks, psq[f]);
         if ((int)threadIdx.x == f) {
             S = s;
             Q = q;
@@ -347,55 +296,30 @@ __global__ __launch_bounds__(WG) void apply(const Apply a) {
     a.out[i] = clamp((float)z, a.clip);
 }
 
-static bool aligned(const void *p, uintptr_t al) { return ((uintptr_t)p & (al - 1)) == 0; }
-
-// the number of workgroups of a ring; false on a bad shape
-static bool plan(const uavx_norm_ring *r, int64_t &blocks) {
-    if (!r || r->envs < 1 || r->agents < 1 || r->envs > INT32_MAX || r->agents > INT32_MAX) return false;
-    if (r->envs * r->agents > INT32_MAX) return false;
-    blocks = (r->envs * r->agents + WG - 1) / WG;
-    return true;
-}
-
 // everything the two folds check alike, and the arguments they share
 static bool fold_args(const uavx_norm_ring *ring, int64_t features, int64_t first, int64_t count, uavx_norm_record *record,
                       void *workspace, int64_t workspace_bytes, Fold &a) {
-    int64_t blocks = 0;
-    if (!plan(ring, blocks)) return false;
-    const uavx_norm_ring &r = *ring;
-    if (r.slots < 2 || r.slots > INT32_MAX || r.learners < 1 || r.learners > r.agents) return false;
-    if (!r.done || (r.skip == nullptr) != (r.ended == nullptr)) return false;
+    if (!ring_view<WG>(ring, a)) return false;
+    const int64_t blocks = a.blocks;
     if (features < 1 || features > MAXF) return false;
-    if (first < 0 || count <= first || count - first > r.slots - 1) return false;
+    if (first < 0 || count <= first || count - first > a.slots - 1) return false;
     if (!record || !workspace || !aligned(record, 8) || !aligned(workspace, 8)) return false;
     if (workspace_bytes < 8 * (2 * features + 1) * blocks) return false;
-    a.done = r.done;
-    a.skip = r.skip;
-    a.ended = r.ended;
     a.rec = record;
     a.sum = (double *)workspace;
     a.sq = a.sum + features * blocks;
     a.cnt = (long long *)(a.sq + features * blocks);
-    a.plane = r.envs * r.agents;
-    a.columns = (int32_t)a.plane;
-    a.agents = (int32_t)r.agents;
-    a.learners = (int32_t)r.learners;
-    a.envs = (int32_t)r.envs;
-    a.slots = (int32_t)r.slots;
-    a.start = (int32_t)(first % r.slots);
-    a.prev = first >= 1 ? (int32_t)((first - 1) % r.slots) : -1;
+    a.start = (int32_t)(first % a.slots);
+    a.prev = first >= 1 ? (int32_t)((first - 1) % a.slots) : -1;
     a.steps = (int32_t)(count - first);
-    a.blocks = (int32_t)blocks;
     a.features = (int32_t)features;
     return true;
 }
 
 template <int F>
-static void launch_obs(const Fold &a, hipStream_t st, bool &ok) {
-    hipLaunchKernelGGL((obs_pass<F, false>), dim3((unsigned)a.blocks), dim3(WG), 0, st, a);
-    ok = ok && hipGetLastError() == hipSuccess;
-    hipLaunchKernelGGL((obs_pass<F, true>), dim3((unsigned)a.blocks), dim3(WG), 0, st, a);
-    ok = ok && hipGetLastError() == hipSuccess;
+static int launch_obs(const Fold &a, hipStream_t st) {
+    const int rc = launch(obs_pass<F, false>, a.blocks, WG, st, a);
+    return rc != UAVX_ACTOR_OK ? rc : launch(obs_pass<F, true>, a.blocks, WG, st, a);
 }
 
 static int apply_call(bool returns, const uavx_norm_record *record, const float *in, float *out, int64_t total,
@@ -414,12 +338,7 @@ static int apply_call(bool returns, const uavx_norm_record *record, const float 
     a.eps = eps;
     a.clip = (float)clip;
     const int64_t threads = a.vec + (total - 4 * a.vec);
-    const dim3 grid((unsigned)((threads + WG - 1) / WG));
-    if (returns)
-        hipLaunchKernelGGL(apply<true>, grid, dim3(WG), 0, (hipStream_t)stream, a);
-    else
-        hipLaunchKernelGGL(apply<false>, grid, dim3(WG), 0, (hipStream_t)stream, a);
-    return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
+    return launch(returns ? apply<true> : apply<false>, (threads + WG - 1) / WG, WG, (hipStream_t)stream, a);
 }
 
 }  // namespace uavx_norm_k
@@ -428,17 +347,13 @@ using namespace uavx_norm_k;
 
 extern "C" {
 
-#ifndef UAVX_NORM_SRC_HASH
-#define UAVX_NORM_SRC_HASH ""
-#endif
-// the loader (_norm_lib.py) finds this marker in the file without mapping it
-__attribute__((used)) static const char kBuildInfo[] = "UAVX_NORM_SRC_HASH=" UAVX_NORM_SRC_HASH;
+UAVX_BUILD_MARKER(UAVX_NORM_SRC_HASH);
 
 int uavx_norm_version(void) { return UAVX_NORM_VERSION; }
 
 int uavx_norm_workspace_bytes(const uavx_norm_ring *ring, int64_t features, int64_t *bytes) {
     int64_t blocks = 0;
-    if (!bytes || !plan(ring, blocks) || features < 1 || features > MAXF) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!bytes || !plan<WG>(ring, blocks) || features < 1 || features > MAXF) return UAVX_ACTOR_ERR_INVALID_ARG;
     *bytes = 8 * (2 * features + 1) * blocks;
     return UAVX_ACTOR_OK;
 }
@@ -450,35 +365,28 @@ int uavx_norm_fold_obs(const uavx_norm_ring *ring, const float *obs, int64_t fea
     if (!obs || !aligned(obs, 4)) return UAVX_ACTOR_ERR_INVALID_ARG;
     a.obs = obs;
     const hipStream_t st = (hipStream_t)stream;
-    bool ok = true;
+    int rc = UAVX_ACTOR_OK;
     switch (features) {
-#define UAVX_NORM_CASE(F) case F: launch_obs<F>(a, st, ok); break;
+#define UAVX_NORM_CASE(F) case F: rc = launch_obs<F>(a, st); break;
         UAVX_NORM_CASE(1) UAVX_NORM_CASE(2) UAVX_NORM_CASE(3) UAVX_NORM_CASE(4) UAVX_NORM_CASE(5) UAVX_NORM_CASE(6)
         UAVX_NORM_CASE(7) UAVX_NORM_CASE(8) UAVX_NORM_CASE(9) UAVX_NORM_CASE(10) UAVX_NORM_CASE(11) UAVX_NORM_CASE(12)
         UAVX_NORM_CASE(13) UAVX_NORM_CASE(14) UAVX_NORM_CASE(15) UAVX_NORM_CASE(16)
 #undef UAVX_NORM_CASE
     }
-    if (!ok) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(merge, dim3(1), dim3(WG), 0, st, a, 0);
-    return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
+    return rc != UAVX_ACTOR_OK ? rc : launch(merge, 1, WG, st, a, 0);
 }
 
 int uavx_norm_fold_returns(const uavx_norm_ring *ring, int64_t first, int64_t count, double gamma, double *carry,
                            uavx_norm_record *record, void *workspace, int64_t workspace_bytes, void *stream) {
     Fold a{};
     if (!fold_args(ring, 1, first, count, record, workspace, workspace_bytes, a)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!ring->rew || !aligned(ring->rew, 4) || !carry || !aligned(carry, 8)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!(gamma >= 0.0 && gamma <= 1.0)) return UAVX_ACTOR_ERR_INVALID_ARG;          // false for NaN
-    a.rew = ring->rew;
+    if (!a.rew || !aligned(a.rew, 4) || !carry || !aligned(carry, 8) || !unit(gamma)) return UAVX_ACTOR_ERR_INVALID_ARG;
     a.carry = carry;
     a.gamma = gamma;
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(ret_sum, dim3((unsigned)a.blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(ret_sq, dim3((unsigned)a.blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(merge, dim3(1), dim3(WG), 0, st, a, 1);
-    return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
+    int rc = launch(ret_sum, a.blocks, WG, st, a);
+    if (rc == UAVX_ACTOR_OK) rc = launch(ret_sq, a.blocks, WG, st, a);
+    return rc != UAVX_ACTOR_OK ? rc : launch(merge, 1, WG, st, a, 1);
 }
 
 int uavx_norm_apply_obs(const uavx_norm_record *record, const float *in, float *out, int64_t rows, int64_t features,

@@ -13,10 +13,14 @@
 #include <math.h>
 #include <stdint.h>
 #include "../../include/uavx_ppo.h"
+#include "../common_csrc/uavx_block_reduce.hpp"
+#include "../common_csrc/uavx_entry.hpp"
 
 namespace uavx_ppo_k {
 
-constexpr int WG = UAVX_PPO_BLOCK, WAVE = 64, WAVES = WG / WAVE;
+using namespace uavx_common;
+
+constexpr int WG = UAVX_PPO_BLOCK, WAVES = WG / WAVE;
 static_assert(WG == 256, "the header documents four wavefronts per workgroup");
 constexpr float HALF_LOG_2PI = 0.91893853320467274178f, LOG_2 = 0.69314718055994530942f;
 
@@ -104,25 +108,6 @@ __device__ inline Row row(const Args &a, int64_t b) {
     return x;
 }
 
-// the sum of a workgroup's values, in every thread: lanes by a halving tree, wavefronts through LDS left to right
-__device__ inline double block_sum(double s, double *part) {
-#pragma unroll
-    for (int off = WAVE / 2; off > 0; off >>= 1) s += __shfl_down(s, off, WAVE);
-    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = s;
-    __syncthreads();
-    double r = part[0];
-#pragma unroll
-    for (int w = 1; w < WAVES; ++w) r += part[w];
-    return r;
-}
-
-// the total of `count` per-workgroup partials, in every thread of the calling workgroup
-__device__ inline double total(const double *__restrict__ partial, int count, double *part) {
-    double s = 0.0;
-    for (int i = threadIdx.x; i < count; i += WG) s += partial[i];
-    return block_sum(s, part);
-}
-
 __global__ __launch_bounds__(WG) void rows(const Args a) {
     __shared__ double part[4][WAVES];
     const int64_t b = (int64_t)blockIdx.x * WG + threadIdx.x;
@@ -138,19 +123,19 @@ __global__ __launch_bounds__(WG) void rows(const Args a) {
     }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const double t = block_sum(s[k], part[k]);
+        const double t = block_sum<WG>(s[k], part[k]);
         if (threadIdx.x == 0) a.partial[(int64_t)k * a.blocks + blockIdx.x] = t;
     }
 }
 
 __global__ __launch_bounds__(WG) void grads(const Args a) {
     __shared__ double part[4][WAVES];
-    const double W = total(a.partial, a.blocks, part[0]);
+    const double W = total<WG>(a.partial, a.blocks, part[0]);
     const double D = W < 1.0 ? 1.0 : W;           // max(1, W); a NaN W stays a NaN, as under torch's clamp
     if (blockIdx.x == 0) {                         // uniform over the workgroup
-        const double S = total(a.partial + a.blocks, a.blocks, part[1]);
-        const double Q = total(a.partial + 2 * (int64_t)a.blocks, a.blocks, part[2]);
-        const double P = total(a.partial + 3 * (int64_t)a.blocks, a.blocks, part[3]);
+        const double S = total<WG>(a.partial + a.blocks, a.blocks, part[1]);
+        const double Q = total<WG>(a.partial + 2 * (int64_t)a.blocks, a.blocks, part[2]);
+        const double P = total<WG>(a.partial + 3 * (int64_t)a.blocks, a.blocks, part[3]);
         if (threadIdx.x == 0) {
             a.scalars[0] = (float)(-S / D);
             a.scalars[1] = (float)(Q / D);
@@ -173,8 +158,6 @@ __global__ __launch_bounds__(WG) void grads(const Args a) {
     a.g_v[b] = (k * a.vf_coef) * x.dv;
 }
 
-static bool aligned(const void *p, uintptr_t al) { return ((uintptr_t)p & (al - 1)) == 0; }
-
 static bool count(int64_t n) { return n >= 1 && n <= INT32_MAX; }
 
 static bool coefficient(double x) { return x >= 0.0 && x <= 1.7976931348623157e308; }     // false for NaN and inf
@@ -185,11 +168,7 @@ using namespace uavx_ppo_k;
 
 extern "C" {
 
-#ifndef UAVX_PPO_SRC_HASH
-#define UAVX_PPO_SRC_HASH ""
-#endif
-// the loader (_ppo_lib.py) finds this marker in the file without mapping it
-__attribute__((used)) static const char kBuildInfo[] = "UAVX_PPO_SRC_HASH=" UAVX_PPO_SRC_HASH;
+UAVX_BUILD_MARKER(UAVX_PPO_SRC_HASH);
 
 int uavx_ppo_version(void) { return UAVX_PPO_VERSION; }
 
@@ -200,11 +179,8 @@ int uavx_ppo_sample(const float *mean, const float *log_std, const float *eps, i
     if (!aligned(mean, 8) || !aligned(log_std, 8) || !aligned(eps, 8) || !aligned(u_out, 8) || !aligned(action_out, 8) ||
         !aligned(logp_out, 4))
         return UAVX_ACTOR_ERR_INVALID_ARG;
-    const int64_t blocks = (rows_ + WG - 1) / WG;
-    hipLaunchKernelGGL(sample, dim3((unsigned)blocks), dim3(WG), 0, (hipStream_t)stream, (const float2 *)mean,
-                       (const float2 *)log_std, (const float2 *)eps, (int32_t)rows_, (float2 *)u_out, logp_out,
-                       (float2 *)action_out);
-    return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
+    return launch(sample, (rows_ + WG - 1) / WG, WG, (hipStream_t)stream, (const float2 *)mean, (const float2 *)log_std,
+                  (const float2 *)eps, (int32_t)rows_, (float2 *)u_out, logp_out, (float2 *)action_out);
 }
 
 int uavx_ppo_loss_workspace_bytes(int64_t B, int64_t *bytes) {
@@ -252,11 +228,8 @@ int uavx_ppo_loss(const float *mean, const float *log_std, const float *v, const
     a.vf_coef = (float)vf_coef;
     a.ent_coef = (float)ent_coef;
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(rows, dim3((unsigned)blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(grads, dim3((unsigned)blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    return UAVX_ACTOR_OK;
+    const int rc = launch(rows, blocks, WG, st, a);
+    return rc != UAVX_ACTOR_OK ? rc : launch(grads, blocks, WG, st, a);
 }
 
 }  // extern "C"

@@ -14,11 +14,18 @@ import pytest
 from gym_uav_collision_avoidance_amd import _native
 
 PACKAGE = "gym_uav_collision_avoidance_amd"
-# module -> (source_hash() with no HIPCC / ARCH / HIPFLAGS override, len(_sources())) before the loaders shared a class
+# module -> (source_hash() with no HIPCC / ARCH / HIPFLAGS override, len(_sources())) before the loaders shared a class.  The
+# entries of _clip_lib, _gae_lib and _ppo_lib moved once since, on purpose: when their block reduction, ring view and
+# entry-point plumbing went into the headers of common_csrc/, their code changed and the shared headers joined their sources
+# (0c0bee4070800ce1, 8ca5c55ca3b9bf76 and 48649d4f3524b361 with 3 sources each before that).  The other four did not move.
 IDENTITY = {"_lib": ("c85b3516db0d8e1b", 18), "_actor_lib": ("17c0e2c29cadcdb4", 23), "_prio_lib": ("3e2046d3591a64b0", 4),
-            "_keywalk_lib": ("f39cb6f50fa5a02e", 4), "_clip_lib": ("0c0bee4070800ce1", 3), "_gae_lib": ("8ca5c55ca3b9bf76", 3),
-            "_ppo_lib": ("48649d4f3524b361", 3)}
+            "_keywalk_lib": ("f39cb6f50fa5a02e", 4), "_clip_lib": ("d2bdf6f7b75e018d", 5), "_gae_lib": ("6112f570b1b9d4de", 6),
+            "_ppo_lib": ("8c24b70afaec9246", 5)}
 DECLARED = [m for m in IDENTITY if m != "_lib"]
+# the libraries that share the headers of common_csrc/ -> the headers each one's source includes, in the order it declares
+SHARED = {"_clip_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp"), "_ppo_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp"),
+          "_gae_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp", "uavx_ring_view.hpp"),
+          "_norm_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp", "uavx_ring_view.hpp")}
 
 
 def _module(name):
@@ -119,6 +126,59 @@ def test_library_class_on_a_toy_library(tmp_path, monkeypatch):
         lib.build()
     assert glob.glob(str(tmp_path / "*.tmp*")) == []
     assert os.path.exists(lib.path) and not lib.up_to_date()   # the last good build stays in place, and stays stale
+
+
+TOY_SHARED = "/* what two toys would share */\nstatic int toy_twice(int a) { return a + a; }\n"
+
+
+def test_library_class_with_a_shared_source(tmp_path):
+    shared = tmp_path / "elsewhere" / "toy_shared.hpp"         # a path passes through, as csrc does
+    shared.parent.mkdir()
+    shared.write_text(TOY_SHARED)
+    src = tmp_path / "toy.hip"
+    src.write_text('#include "elsewhere/toy_shared.hpp"\n' + TOY_C.replace("a + b", "toy_twice(a) + b - a"))
+    (tmp_path / "toy.h").write_text(TOY_H)
+    (tmp_path / "Makefile").write_text(TOY_MAKEFILE)
+    plain = _toy(tmp_path)
+    lib = _native.Library(str(tmp_path), "libtoy.so", b"TOY_SRC_HASH", plain.units, shared=(str(shared),))
+    assert plain.shared == [] and plain.sources() == [str(src), str(tmp_path / "toy.h")]      # the default: as before
+    assert lib.sources() == plain.sources() + [str(shared)]                                    # last, behind the unit headers
+    assert lib.source_hash() != plain.source_hash()
+    assert lib.load().toy_add(2, 3) == 5 and lib.up_to_date()
+    srchash = lib.source_hash()
+    shared.write_text(TOY_SHARED.replace("what two toys would share", "the same,   reworded"))
+    assert lib.source_hash() == srchash and lib.up_to_date()   # a comment is not code, there neither
+    shared.write_text(TOY_SHARED.replace("a + a", "2 * a"))
+    assert lib.source_hash() != srchash and not lib.up_to_date()
+    assert plain.source_hash() != srchash                      # the library without `shared` never saw the file
+    # a name is a file of the package's common_csrc/
+    named = _native.Library(str(tmp_path), "libtoy.so", b"TOY_SRC_HASH", plain.units, shared=("uavx_entry.hpp",))
+    assert named.sources()[-1] == os.path.join(_native.PACKAGE, "common_csrc", "uavx_entry.hpp")
+
+
+# ---- one copy of what the clip, gae, ppo and norm libraries share ------------------------------------------------------------
+
+@pytest.mark.parametrize("name", sorted(SHARED))
+def test_shared_headers_are_sources_and_the_only_copy(name):
+    m = _module(name)
+    common = os.path.join(_native.PACKAGE, "common_csrc")
+    assert sorted(os.listdir(common)) == sorted(set(sum(SHARED.values(), ())))                  # headers only: no Makefile
+    assert not any(w in f for f in os.listdir(common) for w in ("norm", "gae", "ppo", "clip"))
+    hip, = glob.glob(os.path.join(m.CSRC, "*.hip"))
+    text = open(hip).read()
+    included = re.findall(r'^#include "\.\./common_csrc/([^"]+)"$', text, re.M)
+    assert tuple(included) == SHARED[name]                     # what it includes is what it declares ...
+    assert m._sources()[-len(included):] == [os.path.join(common, h) for h in included]         # ... last in its sources
+    for h in included:                                         # no shared header includes a further one
+        assert "common_csrc" not in open(os.path.join(common, h)).read().split("#pragma once", 1)[1], h
+    hdr = re.search(r"^HDR := (.*)$", open(os.path.join(m.CSRC, "Makefile")).read(), re.M).group(1).split()
+    assert hdr[-len(included):] == [f"../common_csrc/{h}" for h in included]
+    for word in ("__shfl_down", "hipGetLastError", "hipLaunchKernelGGL", "kBuildInfo"):
+        assert word not in text, word
+    # no definition of these (a return type in front of the name), only calls
+    assert not re.search(r"\b(bool|T|double|uint32_t|Column)\s+(aligned|unit|block_sum|total|flags|column)\s*\(", text)
+    if "uavx_ring_view.hpp" in included:                       # (uavx_clip.hip has a plan of its own: a group's block numbers)
+        assert "bool plan(" not in text
 
 
 # ---- the six modules' surface ---------------------------------------------------------------------------------------------

@@ -223,7 +223,9 @@ def test_library_cross_compiles_and_carries_its_source_hash():
     x = _xlib()
     assert os.path.basename(x.LIB_PATH) == "libuavx_norm.so" and os.path.isfile(x.LIB_PATH)
     assert x.HEADER == os.path.join(ROOT, "include", "uavx_norm.h") and x.HEADER in x._sources()
-    assert x._sources()[-1] == os.path.join(ROOT, "include", "uavx_actor.h") and len(x._sources()) == 3
+    assert x._sources()[2] == os.path.join(ROOT, "include", "uavx_actor.h") and len(x._sources()) == 6
+    assert x._sources()[3:] == [os.path.join(ROOT, PKG, "common_csrc", h)        # behind it, what the four small libraries share
+                                for h in ("uavx_block_reduce.hpp", "uavx_entry.hpp", "uavx_ring_view.hpp")]
     assert any(f.endswith(os.path.join("norm_csrc", "uavx_norm.hip")) for f in x._sources())
     blob = open(x.LIB_PATH, "rb").read()
     assert f"UAVX_NORM_SRC_HASH={x.source_hash()}".encode() + b"\0" in blob and b"gfx950" in blob
