@@ -2,7 +2,8 @@
 declared once.  UNITS describes its eleven units -- header, bound ABI version, every exported function with its restype and
 argtypes -- and LIB = _native.Library(...) over them is everything else: sources, hash, build, staleness, load and bind.  The
 module's other names are aliases of that object and of the table.  Its directory is its own, so that the environment library
-and the source hash its profiles carry do not change with it.  There is NO fallback: a missing library or device raises."""
+and the source hash its profiles carry do not change with it; its replay unit shares the replay ring's view and the n-step
+walk of common_csrc/ with the prio and keywalk libraries, and their code enters its source hash.  There is NO fallback: a missing library or device raises."""
 import ctypes
 
 from . import _native
@@ -128,7 +129,8 @@ UNITS = (
  POLICY_GRAD_ABI_VERSION, LEARNER_ABI_VERSION, EXPLORE_ABI_VERSION, NSTEP_ABI_VERSION,
  WGRAD_ABI_VERSION) = (u.abi for u in UNITS)
 
-LIB = _native.Library("actor_csrc", "libuavx_actor.so", b"UAVX_ACTOR_SRC_HASH", UNITS)
+LIB = _native.Library("actor_csrc", "libuavx_actor.so", b"UAVX_ACTOR_SRC_HASH", UNITS,
+                      shared=("uavx_entry.hpp", "uavx_replay_ring.hpp", "uavx_replay_walk.hpp"))
 CSRC, LIB_PATH = LIB.csrc, LIB.path
 load, loaded, build, source_hash, _sources, _up_to_date = (LIB.load, LIB.loaded, LIB.build, LIB.source_hash, LIB.sources,
                                                            LIB.up_to_date)

@@ -1,8 +1,9 @@
 """libuavx_keywalk.so: the n-step walk from the keys of a prioritized sample (include/uavx_keywalk.h),
 declared once: the constants and the structure of its header, its one unit -- header, bound ABI version, every exported
 function with its restype and argtypes -- and LIB = _native.Library(...) over it, which is sources, hash, build, staleness,
-load and bind.  The module's other names are aliases of that object and of the table.  Its directory is its own, so that the
-actor and prio libraries and the source hashes they carry do not change with it.  There is NO fallback: a missing library or
+load and bind.  The module's other names are aliases of that object and of the table.  Its directory is its own; the n-step
+walk itself, the replay ring's view and the entry-point plumbing are common_csrc/'s, shared with the actor library's replay
+unit and the prio library, and their code enters its source hash.  There is NO fallback: a missing library or
 device raises."""
 import ctypes
 
@@ -32,7 +33,8 @@ ABI_VERSION = 1
 
 LIB = _native.Library("keywalk_csrc", "libuavx_keywalk.so", b"UAVX_KEYWALK_SRC_HASH",
                       [_native.unit("key-walk", "uavx_keywalk.h", ABI_VERSION, FUNCTIONS)],
-                      extras=("uavx_replay.h", "uavx_actor.h"))
+                      extras=("uavx_replay.h", "uavx_actor.h"),
+                      shared=("uavx_entry.hpp", "uavx_replay_ring.hpp", "uavx_replay_walk.hpp"))
 CSRC, LIB_PATH, HEADER = LIB.csrc, LIB.path, LIB.units[0].header
 load, loaded, build, source_hash, _sources, _up_to_date, check = (LIB.load, LIB.loaded, LIB.build, LIB.source_hash,
                                                                   LIB.sources, LIB.up_to_date, LIB.check)

@@ -2,8 +2,8 @@
 header, its one unit -- header, bound ABI version, every exported function with its restype and argtypes -- and
 LIB = _native.Library(...) over it, which is sources, hash, build, staleness, load and bind.  The module's other names are
 aliases of that object and of the table.  Its directory is its own; the clip, gae, ppo and norm libraries share the headers of
-common_csrc/, whose code enters the source hash of each of the four, and the env, actor, prio and keywalk libraries share
-nothing with them.  Nothing imports this module until a PPOHeads launches, and importing it neither builds nor maps anything.  There is NO
+common_csrc/, whose code enters the source hash of each of the four; of those headers the actor, prio and keywalk libraries use
+uavx_entry.hpp alone, and the env library none.  Nothing imports this module until a PPOHeads launches, and importing it neither builds nor maps anything.  There is NO
 fallback: a missing library or device raises."""
 import ctypes
 

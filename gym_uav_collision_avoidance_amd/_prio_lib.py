@@ -1,8 +1,9 @@
 """libuavx_prio.so: the prioritized-replay kernels (include/uavx_prio.h), declared once: the constants and
 structures of its header, its one unit -- header, bound ABI version, every exported function with its restype and argtypes
 -- and LIB = _native.Library(...) over it, which is sources, hash, build, staleness, load and bind.  The module's other names
-are aliases of that object and of the table.  Its directory is its own, so that the actor library and the source hash it
-carries do not change with it.  There is NO fallback: a missing library or device raises."""
+are aliases of that object and of the table.  Its directory is its own; the replay ring's view and
+the entry-point plumbing are common_csrc/'s, shared with the actor library's replay unit and the keywalk library, and their
+code enters its source hash.  There is NO fallback: a missing library or device raises."""
 import ctypes
 
 from . import _native
@@ -55,7 +56,7 @@ ABI_VERSION = 1
 
 LIB = _native.Library("prio_csrc", "libuavx_prio.so", b"UAVX_PRIO_SRC_HASH",
                       [_native.unit("prioritized-replay", "uavx_prio.h", ABI_VERSION, FUNCTIONS)],
-                      extras=("uavx_replay.h", "uavx_actor.h"))
+                      extras=("uavx_replay.h", "uavx_actor.h"), shared=("uavx_entry.hpp", "uavx_replay_ring.hpp"))
 CSRC, LIB_PATH, HEADER = LIB.csrc, LIB.path, LIB.units[0].header
 load, loaded, build, source_hash, _sources, _up_to_date, check = (LIB.load, LIB.loaded, LIB.build, LIB.source_hash,
                                                                   LIB.sources, LIB.up_to_date, LIB.check)

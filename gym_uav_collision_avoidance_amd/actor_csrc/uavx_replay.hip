@@ -16,7 +16,8 @@
 //                                 another: the kernel boundary is the only ordering between the two phases, and every
 //                                 search is a bounded loop.
 //
-// The walk.  Once (k, e, i) is chosen every address of the walk is known: step j lies in slot s + j (minus slots past the
+// The walk (nstep_walk of ../common_csrc/uavx_replay_walk.hpp, which uavx_keywalk.hip runs from a prioritized sample's keys as
+// well).  Once (k, e, i) is chosen every address of the walk is known: step j lies in slot s + j (minus slots past the
 // wrap: one compare, no division), clamped to the last step that both n_step and the ring's head allow, so that every load
 // is inside the window whatever the flags will say.  The rew, done and flag loads of ALL steps are issued together and
 // unconditionally, with the start row's observation and action, and the stop is resolved in registers afterwards (a load
@@ -34,21 +35,21 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uavx_nstep.h"
+#include "../common_csrc/uavx_entry.hpp"
+#include "../common_csrc/uavx_replay_ring.hpp"
+#include "../common_csrc/uavx_replay_walk.hpp"
 
 namespace uavx_replay_k {
 
+using namespace uavx_common;
+
 static_assert(UAVX_REPLAY_MAX_ROWS == UAVX_NSTEP_MAX_ROWS && UAVX_REPLAY_SINGLE_ROWS == UAVX_NSTEP_SINGLE_ROWS,
               "one workspace layout and one launch shape behind both interfaces");
-constexpr int WG = UAVX_NSTEP_SINGLE_ROWS, WAVES = WG / 64, OBS = 10;
+constexpr int WG = UAVX_NSTEP_SINGLE_ROWS, WAVES = WG / 64;
 constexpr int64_t MAX_BLOCKS = UAVX_NSTEP_MAX_ROWS / WG;
 static_assert(MAX_BLOCKS <= WG, "one thread per block summary");
 
-struct Args {
-    const float *obs, *act, *rew;
-    const uint8_t *done, *skip, *trunc, *ended;      // skip == NULL: flags packed into done
-    int32_t L, E, N, NL;
-    int64_t count;
-    const int64_t *count_dev;
+struct Args : ReplayView {
     const float *u;
     int32_t cols, n;
     double gamma;
@@ -72,23 +73,6 @@ __device__ inline int32_t pick(float u, int32_t n) {
     if (x >= 2147483648.f) return n - 1;
     const int32_t k = (int32_t)x;
     return k < n - 1 ? k : n - 1;
-}
-
-// the sampling window: span steps, the oldest of them in slot lo_mod
-__device__ inline void window(const Args &a, int32_t &lo_mod, int32_t &span) {
-    int64_t c = a.count_dev ? *a.count_dev : a.count;
-    if (c < 1) c = 1;
-    const int64_t T = a.L - 1, lo = c > T ? c - T : 0;
-    span = (int32_t)(c - lo);
-    lo_mod = (int32_t)(lo % a.L);
-}
-
-// the window's span alone: no 64-bit remainder
-__device__ inline int32_t span_of(const Args &a) {
-    int64_t c = a.count_dev ? *a.count_dev : a.count;
-    if (c < 1) c = 1;
-    const int64_t T = a.L - 1;
-    return (int32_t)(c > T ? T : c);
 }
 
 __device__ inline bool skipped(const Args &a, int32_t s, int32_t e) {
@@ -159,99 +143,15 @@ template <int NMAX, bool PACKED>
 __device__ inline void gather(const Args &a, int64_t j, int32_t s, int32_t e, int32_t i, int32_t kk, int32_t span) {
     // the last step the walk can reach: n_step − 1, or the newest step of the ring if that comes first
     const int32_t rem = span - 1 - kk;
-    const int32_t top = NMAX == 1 ? 0 : (rem < a.n - 1 ? rem : a.n - 1);
-    const int64_t se0 = (int64_t)s * a.E + e, cell0 = se0 * a.N + i;
-    const bool flags = a.truncated != nullptr;
-    float rew[NMAX];
-    uint8_t dn[NMAX], sk[NMAX], en[NMAX], tr[NMAX];      // PACKED: sk holds agent 0's done byte, en and tr are not used
-#pragma unroll
-    for (int t = 0; t < NMAX; ++t) {
-        int32_t st = s + (t < top ? t : top);            // st < 2·slots: top <= span − 1 <= slots − 2
-        if (st >= a.L) st -= a.L;
-        const int64_t se = (int64_t)st * a.E + e, cell = se * a.N + i;
-        rew[t] = a.rew[cell];
-        dn[t] = a.done[cell];
-        if (NMAX == 1) {
-            // a single step stops by itself: its flags are only outputs, loaded below when they are asked for
-            sk[t] = en[t] = tr[t] = 0;
-        } else if (PACKED) {
-            sk[t] = a.done[se * a.N];
-        } else {
-            sk[t] = a.skip[se];
-            en[t] = a.ended[se];
-            tr[t] = a.trunc[se];                         // wanted or not: a load under `flags` would be waited for by itself
-        }
-    }
-    const float2 *__restrict__ x = (const float2 *)(a.obs + cell0 * OBS);
-    float2 xs[OBS / 2], ys[OBS / 2];
-#pragma unroll
-    for (int k = 0; k < OBS / 2; ++k) xs[k] = x[k];
-    const float2 act = *(const float2 *)(a.act + cell0 * 2);
-    // every load above is issued before the first of them is waited for: left to itself the scheduler starts resolving
-    // step 0 after half the loads, which puts a wait for memory between the two halves.  (A single step resolves nothing,
-    // and its next_state load belongs with the others.)
-    if (NMAX > 1) __builtin_amdgcn_sched_barrier(0);
-
-    // the stop, in registers: nothing below loads, and every step is computed and then selected, so that there is no
-    // conditional block for the compiler to sink a step's loads into
-    double R = -0.0, g = 1.0;                            // −0 + x is x for every x, a reward of −0 included
-    int32_t len = 1;
-    bool run = true;
-    uint8_t d_last = 0, tr_last = 0, en_last = 0;
-#pragma unroll
-    for (int t = 0; t < NMAX; ++t) {
-        const bool ended = PACKED ? (sk[t] & 4) != 0 : en[t] != 0;
-        const bool trunc = PACKED ? (sk[t] & 8) != 0 : tr[t] != 0;
-        bool stop = t == NMAX - 1 || t >= top || (dn[t] & 1) || ended;
-        if (t + 1 < NMAX) stop = stop || (PACKED ? (sk[t + 1] & 2) != 0 : sk[t + 1] != 0);
-        const double Rt = R + g * (double)rew[t], gt = g * a.gamma;
-        R = run ? Rt : R;
-        d_last = run ? (uint8_t)(dn[t] & 1) : d_last;
-        tr_last = run ? (uint8_t)trunc : tr_last;
-        en_last = run ? (uint8_t)ended : en_last;
-        run = run && !stop;
-        g = run ? gt : g;
-        len = run ? t + 2 : len;
-    }
-
-    int32_t s1 = s + len;                                // len <= rem + 1 <= slots − 1
-    if (s1 >= a.L) s1 -= a.L;
-    const float2 *__restrict__ y = (const float2 *)(a.obs + (((int64_t)s1 * a.E + e) * a.N + i) * OBS);
-#pragma unroll
-    for (int k = 0; k < OBS / 2; ++k) ys[k] = y[k];
-    if (NMAX == 1 && flags) {                            // behind the row's other loads, as the one-step sampler has them
-        if (PACKED) {
-            const uint8_t b = a.done[se0 * a.N];
-            tr_last = (b >> 3) & 1;
-            en_last = (b >> 2) & 1;
-        } else {
-            tr_last = a.trunc[se0] != 0;
-            en_last = a.ended[se0] != 0;
-        }
-    }
-    float2 *__restrict__ xo = (float2 *)(a.state + j * OBS);
-    float2 *__restrict__ yo = (float2 *)(a.next_state + j * OBS);
-#pragma unroll
-    for (int k = 0; k < OBS / 2; ++k) {
-        xo[k] = xs[k];
-        yo[k] = ys[k];
-    }
-    *(float2 *)(a.action + j * 2) = act;
-    a.reward[j] = (float)R;
-    a.mask[j] = (float)((1.0 - (double)d_last) * g);
-    if (a.length) a.length[j] = (uint8_t)len;
-    if (flags) {
-        a.truncated[j] = tr_last;
-        a.ended_out[j] = en_last;
-    }
+    nstep_walk<NMAX, PACKED, true>(a, j, s, e, i, NMAX == 1 ? 0 : (rem < a.n - 1 ? rem : a.n - 1));
 }
 
 template <int NMAX, bool PACKED>
 __global__ __launch_bounds__(WG) void sample_small(const Args a) {
     __shared__ uint64_t bal[WAVES];
     const int j = threadIdx.x;
-    int32_t lo_mod, span;
-    window(a, lo_mod, span);
+    const ReplayWindow w = window(a);
+    const int32_t lo_mod = w.lo_mod, span = w.span;
     Pick p{0, 0, 0, 0, false};
     if (j < a.rows) p = draw(a, j, lo_mod, span);
     const uint64_t mine = publish(p.valid, bal);
@@ -268,8 +168,8 @@ __global__ __launch_bounds__(WG) void sample_small(const Args a) {
 __global__ __launch_bounds__(WG) void sample_draw(const Args a) {
     __shared__ uint64_t bal[WAVES];
     const int64_t base = (int64_t)blockIdx.x * WG, j = base + threadIdx.x;
-    int32_t lo_mod, span;
-    window(a, lo_mod, span);
+    const ReplayWindow w = window(a);
+    const int32_t lo_mod = w.lo_mod, span = w.span;
     Pick p{0, 0, 0, 0, false};
     if (j < a.rows) {
         p = draw(a, j, lo_mod, span);
@@ -346,8 +246,6 @@ static const Kernel SMALL[2][UAVX_NSTEP_MAX] = {UAVX_NSTEP_ROW(sample_small, fal
 static const Kernel GATHER[2][UAVX_NSTEP_MAX] = {UAVX_NSTEP_ROW(sample_gather, false), UAVX_NSTEP_ROW(sample_gather, true)};
 #undef UAVX_NSTEP_ROW
 
-static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 static int64_t summary_bytes(int64_t rows) { return ((rows + WG - 1) / WG * (int64_t)sizeof(int2) + 15) / 16 * 16; }
 
 static int64_t workspace_bytes(int64_t rows) {
@@ -374,15 +272,8 @@ int uavx_replay_workspace_bytes(int64_t rows, int64_t *bytes) { return uavx_nste
 
 int uavx_nstep_sample(const uavx_nstep_args *g, void *stream) {
     if (!g) return UAVX_ACTOR_ERR_INVALID_ARG;
-    const uavx_replay_ring *ring = g->ring;
-    if (!ring || !ring->obs || !ring->act || !ring->rew || !ring->done) return UAVX_ACTOR_ERR_INVALID_ARG;
-    const int flags = (ring->skip != nullptr) + (ring->trunc != nullptr) + (ring->ended != nullptr);
-    if (flags != 0 && flags != 3) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (ring->slots < 2 || ring->slots > INT32_MAX || ring->envs < 1 || ring->envs > INT32_MAX || ring->agents < 1 ||
-        ring->agents > INT32_MAX || ring->learners < 1 || ring->learners > ring->agents)
-        return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!aligned(ring->obs, 8) || !aligned(ring->act, 8) || !aligned(ring->rew, 4)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (g->count_dev ? !aligned(g->count_dev, 8) : g->count < 1) return UAVX_ACTOR_ERR_INVALID_ARG;
+    Args a{};
+    if (!replay_view(g->ring, g->count, g->count_dev, a)) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (g->n_step < 1 || g->n_step > UAVX_NSTEP_MAX) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (!(g->gamma > 0.0 && g->gamma <= 1.0)) return UAVX_ACTOR_ERR_INVALID_ARG;              // a NaN is refused too
     if (!(g->recency >= 0.f && g->recency <= 1.f)) return UAVX_ACTOR_ERR_INVALID_ARG;
@@ -399,20 +290,6 @@ int uavx_nstep_sample(const uavx_nstep_args *g, void *stream) {
     if (need > 0 && (!g->workspace || g->workspace_bytes < need || !aligned(g->workspace, 16)))
         return UAVX_ACTOR_ERR_INVALID_ARG;
 
-    Args a{};
-    a.obs = ring->obs;
-    a.act = ring->act;
-    a.rew = ring->rew;
-    a.done = ring->done;
-    a.skip = ring->skip;
-    a.trunc = ring->trunc;
-    a.ended = ring->ended;
-    a.L = (int32_t)ring->slots;
-    a.E = (int32_t)ring->envs;
-    a.N = (int32_t)ring->agents;
-    a.NL = (int32_t)ring->learners;
-    a.count = g->count;
-    a.count_dev = g->count_dev;
     a.u = g->u;
     a.cols = g->u_cols;
     a.n = g->n_step;
@@ -427,19 +304,14 @@ int uavx_nstep_sample(const uavx_nstep_args *g, void *stream) {
     a.length = g->length;
     a.truncated = g->truncated;
     a.ended_out = g->ended;
-    const int packed = ring->skip == nullptr, level = a.n - 1;
+    const int packed = a.skip == nullptr, level = a.n - 1;
     const hipStream_t st = (hipStream_t)stream;
-    if (rows <= WG) {
-        hipLaunchKernelGGL(SMALL[packed][level], dim3(1), dim3((unsigned)((rows + 63) / 64 * 64)), 0, st, a);
-        return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
-    }
+    if (rows <= WG) return launch(SMALL[packed][level], 1, (int)((rows + 63) / 64 * 64), st, a);
     a.summary = (int2 *)g->workspace;
     a.picks = (int4 *)((char *)g->workspace + summary_bytes(rows));
-    const unsigned blocks = (unsigned)((rows + WG - 1) / WG);
-    hipLaunchKernelGGL(sample_draw, dim3(blocks), dim3(WG), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(GATHER[packed][level], dim3(blocks), dim3(WG), 0, st, a);
-    return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP;
+    const int64_t blocks = (rows + WG - 1) / WG;
+    const int rc = launch(sample_draw, blocks, WG, st, a);
+    return rc != UAVX_ACTOR_OK ? rc : launch(GATHER[packed][level], blocks, WG, st, a);
 }
 
 // One step, uniform draws, three columns of uniforms, no length.  With rows = 0 this entry has always answered before it

@@ -1,5 +1,6 @@
-// What the entry points of libuavx_clip.so, libuavx_gae.so, libuavx_ppo.so and libuavx_norm.so do alike on the host: argument
-// checks, launch-and-report in uavx_actor.h's status codes, and the marker of the build's source hash.
+// What the entry points of libuavx_clip.so, libuavx_gae.so, libuavx_ppo.so, libuavx_norm.so, libuavx_prio.so, libuavx_keywalk.so
+// and libuavx_actor.so's replay unit do alike on the host: argument checks, launch-and-report in uavx_actor.h's status codes,
+// and the marker of the build's source hash.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -23,8 +23,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/uavx_prio.h"
+#include "../common_csrc/uavx_entry.hpp"
+#include "../common_csrc/uavx_replay_ring.hpp"
 
 namespace uavx_prio_k {
+
+using namespace uavx_common;
 
 constexpr int FAN = 64, OBS = 10;
 constexpr int LEAF_WG = 256, LEAF_WAVES = LEAF_WG / 64, LEAF_ITERS = FAN / LEAF_WAVES;      // 4 096 entries per workgroup
@@ -39,29 +43,8 @@ struct Levels {
     uint32_t *bmin, *bvalid;         // per level-2 node
 };
 
-struct Ring {
-    const float *obs, *act, *rew;
-    const uint8_t *done, *skip, *trunc, *ended;      // skip == NULL: flags packed into done
-    int32_t L, E, N, NL;
-    int64_t count;
-    const int64_t *count_dev;
-};
-
-struct Window {
-    int64_t c, lo;
-    int32_t lo_mod;
-};
-
-__device__ inline Window window(const Ring &r) {
-    Window w;
-    int64_t c = r.count_dev ? *r.count_dev : r.count;
-    if (c < 1) c = 1;
-    const int64_t T = r.L - 1;
-    w.c = c;
-    w.lo = c > T ? c - T : 0;
-    w.lo_mod = (int32_t)(w.lo % r.L);
-    return w;
-}
+using Ring = ReplayView;
+using Window = ReplayWindow;
 
 // the step slot s belongs to: the k in [lo, lo + slots) with k % slots == s (inside the window when k < c)
 __device__ inline int64_t step_of(const Window &w, int32_t s, int32_t L) {
@@ -438,8 +421,6 @@ __global__ __launch_bounds__(UPDATE_WG) void update_max(const Ring r, uint32_t *
 
 // ---- host ------------------------------------------------------------------------------------------------------------------
 
-static bool aligned(const void *p, uintptr_t a) { return ((uintptr_t)p & (a - 1)) == 0; }
-
 static int64_t up16(int64_t b) { return (b + 15) / 16 * 16; }
 
 // the levels' sizes and, with a base, their places in the caller's memory -> bytes
@@ -462,40 +443,17 @@ static int64_t carve(int64_t n, void *base, Levels &lv) {
 
 // everything a call checks of the shared state; fills r and lv
 static int check_state(const uavx_prio_state *st, Ring &r, Levels &lv) {
-    if (!st) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!st || !replay_view(st->ring, st->count, st->count_dev, r)) return UAVX_ACTOR_ERR_INVALID_ARG;
     const uavx_replay_ring *ring = st->ring;
-    if (!ring || !ring->obs || !ring->act || !ring->rew || !ring->done) return UAVX_ACTOR_ERR_INVALID_ARG;
-    const int flags = (ring->skip != nullptr) + (ring->trunc != nullptr) + (ring->ended != nullptr);
-    if (flags != 0 && flags != 3) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (ring->slots < 2 || ring->slots > INT32_MAX || ring->envs < 1 || ring->envs > INT32_MAX || ring->agents < 1 ||
-        ring->agents > INT32_MAX || ring->learners < 1 || ring->learners > ring->agents)
-        return UAVX_ACTOR_ERR_INVALID_ARG;
     // slots·envs·learners <= 2^26, without overflowing on the way
     if (ring->envs > UAVX_PRIO_MAX_ENTRIES / ring->slots ||
         ring->learners > UAVX_PRIO_MAX_ENTRIES / (ring->slots * ring->envs))
         return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!aligned(ring->obs, 8) || !aligned(ring->act, 8) || !aligned(ring->rew, 4)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (st->count_dev ? !aligned(st->count_dev, 8) : st->count < 1) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (!st->table || !aligned(st->table, 4) || !st->sums || !aligned(st->sums, 16) || !st->rec || !aligned(st->rec, 8))
         return UAVX_ACTOR_ERR_INVALID_ARG;
     if (st->sums_bytes < carve(ring->slots * ring->envs * ring->learners, st->sums, lv)) return UAVX_ACTOR_ERR_INVALID_ARG;
-    r.obs = ring->obs;
-    r.act = ring->act;
-    r.rew = ring->rew;
-    r.done = ring->done;
-    r.skip = ring->skip;
-    r.trunc = ring->trunc;
-    r.ended = ring->ended;
-    r.L = (int32_t)ring->slots;
-    r.E = (int32_t)ring->envs;
-    r.N = (int32_t)ring->agents;
-    r.NL = (int32_t)ring->learners;
-    r.count = st->count;
-    r.count_dev = st->count_dev;
     return UAVX_ACTOR_OK;
 }
-
-static int launched() { return hipGetLastError() == hipSuccess ? UAVX_ACTOR_OK : UAVX_ACTOR_ERR_HIP; }
 
 }  // namespace uavx_prio_k
 
@@ -503,11 +461,7 @@ using namespace uavx_prio_k;
 
 extern "C" {
 
-#ifndef UAVX_PRIO_SRC_HASH
-#define UAVX_PRIO_SRC_HASH ""
-#endif
-// the loader (_prio_lib.py) finds this marker in the file without mapping it
-__attribute__((used)) static const char kBuildInfo[] = "UAVX_PRIO_SRC_HASH=" UAVX_PRIO_SRC_HASH;
+UAVX_BUILD_MARKER(UAVX_PRIO_SRC_HASH);
 
 int uavx_prio_version(void) { return UAVX_PRIO_VERSION; }
 
@@ -521,13 +475,11 @@ int uavx_prio_state_bytes(int64_t entries, int64_t *bytes) {
 int uavx_prio_refresh(const uavx_prio_state *state, void *stream) {
     Ring r{};
     Levels lv{};
-    const int rc = check_state(state, r, lv);
+    int rc = check_state(state, r, lv);
     if (rc != UAVX_ACTOR_OK) return rc;
     const hipStream_t st = (hipStream_t)stream;
-    hipLaunchKernelGGL(refresh_leaves, dim3((unsigned)lv.n2), dim3(LEAF_WG), 0, st, r, state->table, lv, state->rec);
-    if (launched() != UAVX_ACTOR_OK) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(refresh_top, dim3(1), dim3(TOP_WG), 0, st, r, lv, state->rec);
-    return launched();
+    rc = launch(refresh_leaves, lv.n2, LEAF_WG, st, r, state->table, lv, state->rec);
+    return rc != UAVX_ACTOR_OK ? rc : launch(refresh_top, 1, TOP_WG, st, r, lv, state->rec);
 }
 
 int uavx_prio_sample(const uavx_prio_state *state, const uavx_prio_sample_args *g, void *stream) {
@@ -539,7 +491,7 @@ int uavx_prio_sample(const uavx_prio_state *state, const uavx_prio_sample_args *
     const int64_t rows = g->rows;
     if (rows < 0 || rows > UAVX_PRIO_MAX_ROWS) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (g->stratified != 0 && g->stratified != 1) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (g->beta_dev ? !aligned(g->beta_dev, 4) : !(g->beta >= 0.f && g->beta <= 1.f)) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (g->beta_dev ? !aligned(g->beta_dev, 4) : !unit(g->beta)) return UAVX_ACTOR_ERR_INVALID_ARG;
     if ((g->truncated == nullptr) != (g->ended == nullptr)) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (rows == 0) return UAVX_ACTOR_OK;
     if (!g->u || !g->state || !g->action || !g->reward || !g->next_state || !g->mask || !g->key || !g->weight)
@@ -563,22 +515,20 @@ int uavx_prio_sample(const uavx_prio_state *state, const uavx_prio_sample_args *
     a.key = g->key;
     a.weight = g->weight;
     const int64_t per_block = SAMPLE_WG / GROUP;
-    const unsigned blocks = (unsigned)((rows + per_block - 1) / per_block);
-    hipLaunchKernelGGL(sample_rows, dim3(blocks), dim3(SAMPLE_WG), 0, (hipStream_t)stream, r, state->table, lv, state->rec,
-                       a);
-    return launched();
+    return launch(sample_rows, (rows + per_block - 1) / per_block, SAMPLE_WG, (hipStream_t)stream, r, state->table, lv,
+                  state->rec, a);
 }
 
 int uavx_prio_update(const uavx_prio_state *state, const int64_t *key, const float *q, int32_t towers, const float *y,
                      int64_t y_stride, int64_t rows, double alpha, double eps, void *stream) {
     Ring r{};
     Levels lv{};
-    const int rc = check_state(state, r, lv);
+    int rc = check_state(state, r, lv);
     if (rc != UAVX_ACTOR_OK) return rc;
     if (rows < 0 || rows > UAVX_PRIO_MAX_ROWS) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (towers < 1 || towers > UAVX_PRIO_MAX_TOWERS || (!y && towers != 1)) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (y && y_stride < 1) return UAVX_ACTOR_ERR_INVALID_ARG;
-    if (!(alpha >= 0.0 && alpha <= 1.0) || !(eps > 0.0) || !(eps < INFINITY)) return UAVX_ACTOR_ERR_INVALID_ARG;
+    if (!unit(alpha) || !(eps > 0.0) || !(eps < INFINITY)) return UAVX_ACTOR_ERR_INVALID_ARG;
     if (rows == 0) return UAVX_ACTOR_OK;
     if (!key || !aligned(key, 8) || !q || !aligned(q, 4) || !aligned(y, 4)) return UAVX_ACTOR_ERR_INVALID_ARG;
     UpdateArgs a{};
@@ -591,11 +541,9 @@ int uavx_prio_update(const uavx_prio_state *state, const int64_t *key, const flo
     a.alpha = alpha;
     a.eps = eps;
     const hipStream_t st = (hipStream_t)stream;
-    const unsigned blocks = (unsigned)((rows + UPDATE_WG - 1) / UPDATE_WG);
-    hipLaunchKernelGGL(update_clear, dim3(blocks), dim3(UPDATE_WG), 0, st, r, state->table, a);
-    if (launched() != UAVX_ACTOR_OK) return UAVX_ACTOR_ERR_HIP;
-    hipLaunchKernelGGL(update_max, dim3(blocks), dim3(UPDATE_WG), 0, st, r, state->table, state->rec, a);
-    return launched();
+    const int64_t blocks = (rows + UPDATE_WG - 1) / UPDATE_WG;
+    rc = launch(update_clear, blocks, UPDATE_WG, st, r, state->table, a);
+    return rc != UAVX_ACTOR_OK ? rc : launch(update_max, blocks, UPDATE_WG, st, r, state->table, state->rec, a);
 }
 
 }  // extern "C"

@@ -17,14 +17,15 @@ from gym_uav_collision_avoidance_amd import _actor_lib, _native, policy
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 # source_hash() at the commit that folded the weighted critic gradient into uavx_critic_grad.hip, the second commit that moved
 # it on purpose (a056e385b4f6651e before it, from the commit that moved the n-step sampler into uavx_replay.hip;
-# ab517ee91bb05350 before that)
-MERGED_HASH = "17c0e2c29cadcdb4"
+# ab517ee91bb05350 before that), and moved once more, from 17c0e2c29cadcdb4, when uavx_replay.hip took the replay ring's view,
+# the n-step walk and the entry plumbing from common_csrc/
+MERGED_HASH = "c6725b15f59f1983"
 PARENT_SOURCES = [
     "uavx_action_grad.hip", "uavx_actor.hip", "uavx_actor_impl.hpp", "uavx_critic.hip", "uavx_critic_grad.hip",
     "uavx_explore.hip", "uavx_grad_common.hip", "uavx_grad_impl.hpp", "uavx_learner.hip", "uavx_optim.hip",
     "uavx_policy_grad.hip", "uavx_replay.hip", "uavx_actor.h", "uavx_critic.h", "uavx_critic_grad.h", "uavx_optim.h",
     "uavx_replay.h", "uavx_action_grad.h", "uavx_policy_grad.h", "uavx_learner.h", "uavx_explore.h", "uavx_nstep.h",
-    "uavx_wcritic_grad.h"]
+    "uavx_wcritic_grad.h", "uavx_entry.hpp", "uavx_replay_ring.hpp", "uavx_replay_walk.hpp"]
 UNIT_NAMES = ("", "CRITIC_", "GRAD_", "OPTIM_", "REPLAY_", "ACTION_GRAD_", "POLICY_GRAD_", "LEARNER_", "EXPLORE_",
               "NSTEP_", "WGRAD_")
 PARENT_HEADERS = ("uavx_actor.h", "uavx_critic.h", "uavx_critic_grad.h", "uavx_optim.h", "uavx_replay.h",
@@ -59,14 +60,15 @@ def test_hash_and_sources_are_the_parents():
     """Nothing outside the replay unit and the critic-gradient unit moved: every source but uavx_replay.hip and
     uavx_critic_grad.hip has the code it had at 9a32f7c (golden/actor_sources_parent.json, written there by
     golden/make_actor_sources.py), and the only files the library gained are the n-step header and the weighted
-    critic gradient's.  The hash moved twice, each time for one unit: when the n-step sampler joined uavx_replay.hip, and
-    when the weighted critic gradient, until then a restatement of grad_rows in a library of its own, became a template
-    switch of grad_rows."""
+    critic gradient's, and the three headers of common_csrc/ that uavx_replay.hip includes.  The hash moved three times, each
+    time for one unit: when the n-step sampler joined uavx_replay.hip, when the weighted critic gradient, until then a
+    restatement of grad_rows in a library of its own, became a template switch of grad_rows, and when what
+    the replay unit had alike with the prio and keywalk libraries went to common_csrc/ (§21)."""
     sources = _actor_lib._sources()
     assert [os.path.basename(p) for p in sources] == PARENT_SOURCES
     assert all(os.path.isfile(p) for p in sources)
     parent = json.load(open(os.path.join(ROOT, "tests", "golden", "actor_sources_parent.json")))
-    gained = {"uavx_nstep.h", "uavx_wcritic_grad.h"}
+    gained = {"uavx_nstep.h", "uavx_wcritic_grad.h", "uavx_entry.hpp", "uavx_replay_ring.hpp", "uavx_replay_walk.hpp"}
     assert set(PARENT_SOURCES) == set(parent) | gained and not gained & set(parent)
     for p in sources:
         name = os.path.basename(p)

@@ -17,15 +17,23 @@ PACKAGE = "gym_uav_collision_avoidance_amd"
 # module -> (source_hash() with no HIPCC / ARCH / HIPFLAGS override, len(_sources())) before the loaders shared a class.  The
 # entries of _clip_lib, _gae_lib and _ppo_lib moved once since, on purpose: when their block reduction, ring view and
 # entry-point plumbing went into the headers of common_csrc/, their code changed and the shared headers joined their sources
-# (0c0bee4070800ce1, 8ca5c55ca3b9bf76 and 48649d4f3524b361 with 3 sources each before that).  The other four did not move.
-IDENTITY = {"_lib": ("c85b3516db0d8e1b", 18), "_actor_lib": ("17c0e2c29cadcdb4", 23), "_prio_lib": ("3e2046d3591a64b0", 4),
-            "_keywalk_lib": ("f39cb6f50fa5a02e", 4), "_clip_lib": ("d2bdf6f7b75e018d", 5), "_gae_lib": ("6112f570b1b9d4de", 6),
+# (0c0bee4070800ce1, 8ca5c55ca3b9bf76 and 48649d4f3524b361 with 3 sources each before that).  Those of _actor_lib, _prio_lib and
+# _keywalk_lib moved once as well, on purpose: when the replay ring's view and the n-step walk of their three replay units went
+# into common_csrc/ too (17c0e2c29cadcdb4 with 23 sources, 3e2046d3591a64b0 with 4 and f39cb6f50fa5a02e with 4 before that).
+# _lib did not move.
+IDENTITY = {"_lib": ("c85b3516db0d8e1b", 18), "_actor_lib": ("c6725b15f59f1983", 26), "_prio_lib": ("75c3f7d1033d0f00", 6),
+            "_keywalk_lib": ("6da2580c17538898", 7), "_clip_lib": ("d2bdf6f7b75e018d", 5), "_gae_lib": ("6112f570b1b9d4de", 6),
             "_ppo_lib": ("8c24b70afaec9246", 5)}
 DECLARED = [m for m in IDENTITY if m != "_lib"]
 # the libraries that share the headers of common_csrc/ -> the headers each one's source includes, in the order it declares
 SHARED = {"_clip_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp"), "_ppo_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp"),
           "_gae_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp", "uavx_ring_view.hpp"),
-          "_norm_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp", "uavx_ring_view.hpp")}
+          "_norm_lib": ("uavx_block_reduce.hpp", "uavx_entry.hpp", "uavx_ring_view.hpp"),
+          "_actor_lib": ("uavx_entry.hpp", "uavx_replay_ring.hpp", "uavx_replay_walk.hpp"),
+          "_prio_lib": ("uavx_entry.hpp", "uavx_replay_ring.hpp"),
+          "_keywalk_lib": ("uavx_entry.hpp", "uavx_replay_ring.hpp", "uavx_replay_walk.hpp")}
+# the three replay units; the actor library has eleven .hip files, and uavx_replay.hip is the one that shares
+REPLAY = {"_actor_lib": "uavx_replay.hip", "_prio_lib": "uavx_prio.hip", "_keywalk_lib": "uavx_keywalk.hip"}
 
 
 def _module(name):
@@ -156,7 +164,7 @@ def test_library_class_with_a_shared_source(tmp_path):
     assert named.sources()[-1] == os.path.join(_native.PACKAGE, "common_csrc", "uavx_entry.hpp")
 
 
-# ---- one copy of what the clip, gae, ppo and norm libraries share ------------------------------------------------------------
+# ---- one copy of what the clip, gae, ppo and norm libraries share, and of what the three replay units share -------------------
 
 @pytest.mark.parametrize("name", sorted(SHARED))
 def test_shared_headers_are_sources_and_the_only_copy(name):
@@ -164,7 +172,7 @@ def test_shared_headers_are_sources_and_the_only_copy(name):
     common = os.path.join(_native.PACKAGE, "common_csrc")
     assert sorted(os.listdir(common)) == sorted(set(sum(SHARED.values(), ())))                  # headers only: no Makefile
     assert not any(w in f for f in os.listdir(common) for w in ("norm", "gae", "ppo", "clip"))
-    hip, = glob.glob(os.path.join(m.CSRC, "*.hip"))
+    hip, = glob.glob(os.path.join(m.CSRC, REPLAY.get(name, "*.hip")))
     text = open(hip).read()
     included = re.findall(r'^#include "\.\./common_csrc/([^"]+)"$', text, re.M)
     assert tuple(included) == SHARED[name]                     # what it includes is what it declares ...
@@ -179,6 +187,13 @@ def test_shared_headers_are_sources_and_the_only_copy(name):
     assert not re.search(r"\b(bool|T|double|uint32_t|Column)\s+(aligned|unit|block_sum|total|flags|column)\s*\(", text)
     if "uavx_ring_view.hpp" in included:                       # (uavx_clip.hip has a plan of its own: a group's block numbers)
         assert "bool plan(" not in text
+    if name in REPLAY:
+        # no window function, no field-by-field fill of the view from the public ring, no copy of the walk's resolution loop
+        assert not re.search(r"\b\w+\s+(window|span_of|steps_of|replay_view|nstep_walk)\s*\([^;{]*\)\s*\{", text)
+        assert "count_dev ?" not in text and not re.search(r"= *\(int32_t\) *ring->", text) and "ring->obs" not in text
+        assert "run ? Rt : R" not in text and "sched_barrier" not in text
+        walk = open(os.path.join(common, "uavx_replay_walk.hpp")).read()
+        assert walk.count("run ? Rt : R") == 1 and ("nstep_walk<" in text) == ("uavx_replay_walk.hpp" in included)
 
 
 # ---- the six modules' surface ---------------------------------------------------------------------------------------------

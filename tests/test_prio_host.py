@@ -76,8 +76,10 @@ def test_the_actor_library_is_untouched():
     from gym_uav_collision_avoidance_amd import _actor_lib
     assert len(_actor_lib.UNITS) == 11 and _actor_lib.UNITS[-1].word == "weighted critic-gradient"
     assert not any("prio" in os.path.basename(f) for f in _actor_lib._sources())
-    assert _actor_lib.source_hash() == "17c0e2c29cadcdb4"
-    # (a056e385b4f6651e before this library existed; moved once since, when the weighted critic gradient became a unit)
+    assert _actor_lib.source_hash() == "c6725b15f59f1983"
+    # (a056e385b4f6651e before this library existed; moved twice since: when the weighted critic gradient became a unit, and from
+    # 17c0e2c29cadcdb4 when its replay unit and this library took the ring's view from common_csrc/.  No file of prio_csrc/ is among
+    # its sources, as before)
     pkg = os.path.join(ROOT, "gym_uav_collision_avoidance_amd")
     assert os.path.isdir(os.path.join(pkg, "prio_csrc")) and not os.path.exists(os.path.join(pkg, "replay_csrc"))
 
